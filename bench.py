@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the Flash-Attention hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline figure needs: set up, settle and warm up, time the K steps, print the line.
+  --full          also run the secondary measurements: the opt-in folded-scale forward, the fwd+bwd leg with the
+                  backward's per-kernel times (`roofline_bwd`), and the CPU baseline (--no-bwd / --no-cpu-baseline drop
+                  the last two).
+  --dump-outputs  after the timed steps, write what the last timed step computed -- O and the row statistics m, l that
+                  the forward returns (rank 0's; a suffix _<i> for its i-th launch when it has several) -- to
+                  DIR/<name>.npy in float32.  The inputs are seeded, so equal arguments give equal inputs in every run.
+                  Past 64 MB in all, every array is cut to a fixed sample: the sorted distinct flat indices among
+                  numpy.random.default_rng(0).integers(0, size, share), the same in every run.
 
 Metric (BASELINE.json): attention TFLOP/s (+ GB/s), forward and forward+backward, at
 E=64, L=4096, H=4, B=4.  Workload at N=1 = BASELINE config C2: bf16, non-causal, forward -- a
@@ -16,10 +26,10 @@ independent); the optional all-gather of O is timed sepa
                      rectangles per rank, pointer offsets only; a step = the rank's rectangles, one launch each.
 
 Extra objects on the JSON line:
-  roofline     -- dominant kernel (fa_fwd_duo_kernel at C2 since round 4; fa_fwd_w64_kernel at C3-C5): algorithmic FLOPs per launch / average launch
+  roofline     -- (every run) dominant kernel (fa_fwd_duo_kernel at C2 since round 4; fa_fwd_w64_kernel at C3-C5): algorithmic FLOPs per launch / average launch
                   duration measured here with HIP events on the launch stream, against the dense
                   bf16 MFMA peak (2516.6 TFLOP/s = 256 CU x 4 SIMD x 1024 FLOP/clk x 2.4 GHz).
-  cpu_baseline -- the oracle's fp32 port of the reference's naive attention
+  cpu_baseline -- (--full) the oracle's fp32 port of the reference's naive attention
                   (benchmarks/main.jl:26-43) timed on this host's cores (rank 0, N=1 only).
 """
 from __future__ import annotations
@@ -61,14 +71,43 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bwd", action="store_true", help="skip the (untimed-region) fwd+bwd leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: folded-scale forward, fwd+bwd leg with per-kernel backward times, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (O, m, l) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-bwd", action="store_true", help="with --full: skip the (untimed-region) fwd+bwd leg")
     ap.add_argument("--gather", action="store_true", help="also time the optional all-gather of O (N>1)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed: run the step back to back for this long BEFORE the W warm-up steps, so that the timed K steps "
                          "see the sustained (power-managed) clock instead of the first milliseconds after idle; 0 = off")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_ELEMS = 15 << 20                              # float32 elements: 60 MiB of data, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, parts):
+    """--dump-outputs: O, m and l of every launch of the last timed step as float32 .npy (sampled past DUMP_MAX_ELEMS)."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for i, t in enumerate(parts):
+        for n in ("o", "ms", "ls"):
+            arrays[n + (f"_{i}" if i else "")] = t[n]
+    total = sum(a.numel() for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        out = a.detach()
+        if total > DUMP_MAX_ELEMS:                       # a fixed sample: same indices for the same shapes in every run
+            share = max(1, a.numel() * DUMP_MAX_ELEMS // total)
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), share))
+            out = out.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), out.float().cpu().numpy())
 
 
 def cpu_baseline(E, L, H, B):
@@ -207,6 +246,8 @@ def main():
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     t_wall, t_dev = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, parts)          # before --full's legs rewrite o, ms, ls
 
     esz = 2 if dtn != "f32" else 4
     f_fwd = attention_flops(E, L, L, QH, B, causal=causal, kv_lens=kv_lens)      # weak: per GPU; strong: the global problem
@@ -225,7 +266,7 @@ def main():
     extra = {}
     # ---- the opt-in forward variant (NNOP_FWD_EXACT_SCALE=0: scale * log2e folded into Q, rounded once -- outside the parity
     # tolerance on large logits), reported beside the default; `value` is the default's -------------------
-    if not strong and parts and dtn != "f32":
+    if args.full and not strong and parts and dtn != "f32":
         prev = pkg._lib.debug_set("fwd_exact_scale", 0)
         try:
             settle(step)
@@ -244,7 +285,7 @@ def main():
         extra["fwd_folded_scale_note"] = "opt-in variant (NNOP_FWD_EXACT_SCALE=0), this rank, by HIP events; not the default and not `value`"
 
     # ---- fwd+bwd leg (outside the timed region above; same inputs) -----------------------------
-    if not args.no_bwd and not strong:
+    if args.full and not args.no_bwd and not strong:
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         ws = torch.empty(pkg.bwd_workspace_bytes(q, k, v, causal=causal), dtype=torch.uint8, device=dev)
         fb = lambda: (pkg.fa_fwd_into(o, ms, ls, q, k, v, causal=causal, kpad_mask=kpad),
@@ -403,7 +444,7 @@ def main():
                      "hbm_frac_at_this_rate": round(by_mine / n_launch / kern_s / 1e9 / HBM_PEAK_GBS, 4)},
     }
     out.update(extra)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(64, 4096, 4, 4)
         out["cpu_baseline"]["gpu_speedup_fwd"] = round(value / max(out["cpu_baseline"]["value"], 1e-12), 1)
     print(json.dumps(out), flush=True)

@@ -35,7 +35,7 @@ def compile_asm(src, extra):
     for f in sorted(glob.glob(os.path.join(CSRC, "*.h*")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(CSRC, src)]):
         hsh.update(f.encode()); hsh.update(open(f, "rb").read())
     hsh.update(" ".join(extra).encode())
-    cache = os.path.join(tempfile.gettempdir(), "nnop_asm_cache")
+    cache = os.path.join(tempfile.gettempdir(), f"nnop_asm_cache_{os.getuid()}")      # per user: another account's cache is not writable
     os.makedirs(cache, exist_ok=True)
     hit = os.path.join(cache, f"{src}.{hsh.hexdigest()[:24]}.s")
     if os.path.exists(hit):

@@ -1,8 +1,8 @@
-cd /root/repo; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 for asc in 0 1; do for c in c5 c3; do
   out=gpurun_out/order_${c}_$asc; rm -rf $out; mkdir -p $out
-  NNOP_FWD_PERSIST_ASC=$asc rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/f -- python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-bwd > /dev/null 2> $out/err
-  NNOP_FWD_PERSIST_ASC=$asc rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/w -- python3 bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-bwd > /dev/null 2>> $out/err
+  NNOP_FWD_PERSIST_ASC=$asc rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/f -- python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-bwd > /dev/null 2> $out/err
+  NNOP_FWD_PERSIST_ASC=$asc rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/w -- python3 bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-bwd > /dev/null 2>> $out/err
   python3 - $out $c $asc <<'PY'
 import csv, glob, sys
 out, c, asc = sys.argv[1:]

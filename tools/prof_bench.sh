@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 CFG=${1:-c2}; shift || true
 OUT=gpurun_out/prof_$CFG; rm -rf $OUT; mkdir -p $OUT
 STEPS=100; [ "$CFG" != "c2" ] && STEPS=10
-BENCH="python3 bench.py --config $CFG --steps $STEPS --warmup 5 --no-cpu-baseline --no-bwd $*"
+BENCH="python3 bench.py --full --config $CFG --steps $STEPS --warmup 5 --no-cpu-baseline --no-bwd $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_traced.json 2> $OUT/trace.err
 i=0
 # (at most 4 counters per pass, so that no pass is silently split into several)

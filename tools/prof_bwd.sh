@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 CFG=${1:-c2}
 OUT=gpurun_out/prof_bwd_$CFG; rm -rf $OUT; mkdir -p $OUT
 STEPS=40; [ "$CFG" != "c2" ] && STEPS=8
-BENCH="python3 bench.py --config $CFG --steps $STEPS --warmup 4 --settle-ms 200 --no-cpu-baseline"
+BENCH="python3 bench.py --full --config $CFG --steps $STEPS --warmup 4 --settle-ms 200 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_traced.json 2> $OUT/trace.err
 i=0
 for c in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES" "FETCH_SIZE" "WRITE_SIZE"; do
