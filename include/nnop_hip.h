@@ -63,11 +63,13 @@ typedef enum nnop_status {
     NNOP_ERR_SHAPE          = -8,  /* a non-positive / overflowing dimension                                 */
     NNOP_ERR_WORKSPACE      = -9,  /* workspace smaller than nnop_fa_bwd_workspace_bytes                      */
     NNOP_ERR_HIP            = -10, /* HIP runtime error at launch (hipGetLastError)                          */
-    NNOP_ERR_ALIGN          = -11  /* a tensor or workspace base address is not aligned as the kernels need:
+    NNOP_ERR_ALIGN          = -11, /* a tensor or workspace base address is not aligned as the kernels need:
                                       16 bytes for q, k, v, o, the gradients, pair / dpair and the workspace
                                       (the MFMA kernels move them with 16-byte vector accesses and LDS-DMA),
                                       the element size for ms, ls.  Embedding dims that run the plain-HIP
                                       kernels (not 16 / 32 / 64 / 128 / 256) need element alignment only.      */
+    NNOP_ERR_OPTS           = -12  /* invalid attention options (nnop_fa_opts): a reserved field is not 0, or a window
+                                      side is below -1 (ABI version 7)                                          */
 } nnop_status;
 
 /*
@@ -110,6 +112,31 @@ int nnop_fa_fwd(const nnop_fa_desc* d,
                 nnop_stream_t stream);
 
 /*
+ * Per-call attention options (ABI version 7), for nnop_fa_fwd_ex / nnop_fa_bwd_ex.  NULL means "no options" and is exactly
+ * nnop_fa_fwd / nnop_fa_bwd.
+ *
+ * Sliding-window (local) attention, flash-attn's `window_size` convention: query row i sees key j only if
+ *     (window_left  < 0 || j >= i - window_left)  and  (window_right < 0 || j <= i + window_right)
+ * on top of the causal rule (j <= i) and kpad_mask.  -1 = that side is unbounded; a value below -1 is NNOP_ERR_OPTS.
+ * The window is TOP-LEFT aligned whatever QL and KL are: query i lines up with key i, as the causal mask does
+ * (src/attention.jl:41-43).  A row that sees no key follows the usual convention (NaN in o, -inf in ms, dq = 0).
+ * A side that removes no key (window_left >= QL - 1, window_right >= KL - 1, or any window_right >= 0 under causal) counts as
+ * unbounded; when both sides are, the call is exactly the call without options.  A window needs no extra workspace.
+ * `reserved` must be all 0 (room for later per-call options).
+ */
+typedef struct nnop_fa_opts {
+    int32_t window_left;
+    int32_t window_right;
+    int32_t reserved[6];
+} nnop_fa_opts;
+
+int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts,
+                   void* o, void* ms, void* ls,
+                   const void* q, const void* k, const void* v,
+                   const void* pair, const uint8_t* kpad_mask,
+                   nnop_stream_t stream);
+
+/*
  * Scratch the backward needs (replaces the reference's internal Δ_scaled / δ temporaries,
  * src/attention_bwd.jl:224-225).  Returns 0 for an invalid descriptor.
  */
@@ -138,6 +165,16 @@ int nnop_fa_bwd(const nnop_fa_desc* d,
                 const void* pair, const uint8_t* kpad_mask,
                 void* workspace, size_t workspace_bytes,
                 nnop_stream_t stream);
+/* The same with per-call options (nnop_fa_opts above; NULL = none).  The forward and the backward of one problem take the
+ * same options.  With a window and a pair bias the backward never uses the staged scratch of
+ * nnop_fa_bwd_workspace_bytes_pair (it takes the direct path whatever `workspace_bytes` is). */
+int nnop_fa_bwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts,
+                   void* dq, void* dk, void* dv, void* dpair,
+                   const void* d_o, const void* o, const void* ms, const void* ls,
+                   const void* q, const void* k, const void* v,
+                   const void* pair, const uint8_t* kpad_mask,
+                   void* workspace, size_t workspace_bytes,
+                   nnop_stream_t stream);
 
 /*
  * Llama rotary embedding: contract of NNop._llama_rope(q, k, cos, sin; bwd)
@@ -227,6 +264,8 @@ size_t nnop_norm_bwd_workspace_bytes(const nnop_norm_desc* d, int layer_norm);
  * (tail of the first batch, whole batches, head of the last batch); each is a problem of its own for nnop_fa_fwd / nnop_fa_bwd at the
  * element offsets below -- pointer arithmetic only, no copies, no collective.  Host-only: touches no device.
  * Returns the number of rectangles written to `out` (0..3), or a negative nnop_status for an invalid descriptor / world / rank.
+ * Rectangles split only batch and heads, never the sequence axes: a caller with per-call options (nnop_fa_opts, e.g. a window)
+ * passes the same options to nnop_fa_fwd_ex / nnop_fa_bwd_ex of every rectangle.
  */
 typedef struct nnop_fa_shard {
     nnop_fa_desc desc;   /* the rectangle as a problem: batch, qh, kh replaced; everything else as in the full problem */
@@ -250,7 +289,7 @@ int nnop_shared_memory(int device, uint64_t* bytes);
 const char* nnop_strerror(int status);
 
 /* ABI version of this header: bumped on any incompatible change. */
-#define NNOP_HIP_ABI_VERSION 6
+#define NNOP_HIP_ABI_VERSION 7
 int nnop_abi_version(void);
 
 #ifdef __cplusplus

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NNOP_LIB_PATH") or os.path.join(_HERE, "lib", "libnnop_hip.so")
 
 # NNOP_HIP_ABI_VERSION of the header this binding was written against; load() refuses another library
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # nnop_dtype (include/nnop_hip.h)
 NNOP_F32, NNOP_F16, NNOP_BF16 = 0, 1, 2
@@ -32,12 +32,15 @@ NNOP_ERR_SHAPE = -8
 NNOP_ERR_WORKSPACE = -9
 NNOP_ERR_HIP = -10
 NNOP_ERR_ALIGN = -11
+NNOP_ERR_OPTS = -12
 
 EXPORTED_SYMBOLS = (
     "nnop_fa_fwd",
     "nnop_fa_bwd_workspace_bytes",
     "nnop_fa_bwd_workspace_bytes_pair",
     "nnop_fa_bwd",
+    "nnop_fa_fwd_ex",
+    "nnop_fa_bwd_ex",
     "nnop_llama_rope",
     "nnop_online_softmax",
     "nnop_online_softmax_bwd",
@@ -54,7 +57,8 @@ EXPORTED_SYMBOLS = (
 
 
 # Test-only hooks (csrc/nnop_debug.h): exported by the library, deliberately NOT in the public header.
-DEBUG_SYMBOLS = ("nnop_debug_set", "nnop_debug_dev_build", "nnop_debug_fwd_form", "nnop_debug_bwd_form")
+DEBUG_SYMBOLS = ("nnop_debug_set", "nnop_debug_dev_build", "nnop_debug_fwd_form", "nnop_debug_bwd_form",
+                 "nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex")
 FWD_FORMS = {0: "fa_fwd_kernel", 1: "fa_fwd_split_kernel", 2: "fa_fwd_w64_kernel", 3: "fa_fwd_generic_kernel", 4: "fa_fwd_duo_kernel"}
 # keys of nnop_debug_set == enum TuneKey (csrc/tuning.hpp)
 TUNE_KEYS = {"fwd_split": 0, "fwd_nw": 1, "fwd_w64": 2, "bwd_big7": 3, "norm_bwd_cap": 4, "bwd_nw": 5,
@@ -77,6 +81,11 @@ class FaDesc(C.Structure):
 FaShard._fields_ = [("desc", FaDesc), ("b0", C.c_int32), ("b1", C.c_int32), ("kh0", C.c_int32), ("kh1", C.c_int32),
                     ("q_off", C.c_uint64), ("kv_off", C.c_uint64), ("row_off", C.c_uint64), ("mask_off", C.c_uint64),
                     ("pair_off", C.c_int64)]
+
+
+class FaOpts(C.Structure):
+    """struct nnop_fa_opts (ABI version 7): per-call options of nnop_fa_fwd_ex / nnop_fa_bwd_ex"""
+    _fields_ = [("window_left", C.c_int32), ("window_right", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 class RopeDesc(C.Structure):
@@ -133,6 +142,12 @@ def load():
     lib.nnop_fa_bwd.restype = C.c_int
     lib.nnop_fa_bwd.argtypes = [C.POINTER(FaDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                 u8p, vp, C.c_size_t, vp]
+    op = C.POINTER(FaOpts)
+    lib.nnop_fa_fwd_ex.restype = C.c_int
+    lib.nnop_fa_fwd_ex.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
+    lib.nnop_fa_bwd_ex.restype = C.c_int
+    lib.nnop_fa_bwd_ex.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   u8p, vp, C.c_size_t, vp]
     lib.nnop_llama_rope.restype = C.c_int
     lib.nnop_llama_rope.argtypes = [C.POINTER(RopeDesc), vp, vp, vp, vp, vp, vp, C.c_float, vp]
     lib.nnop_online_softmax.restype = C.c_int
@@ -167,6 +182,10 @@ def load():
         if hasattr(lib, name):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int]
+    for name in ("nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex"):
+        if hasattr(lib, name):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.POINTER(FaOpts), C.c_int, C.c_int]
     _lib = lib
     return lib
 
@@ -200,17 +219,43 @@ def dev_build() -> bool:
     return bool(load().nnop_debug_dev_build())
 
 
-def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False) -> str:
+def fa_opts(window=None, desc=None):
+    """FaOpts for a window (left, right) -- flash-attn's `window_size`, -1 = unbounded side -- or None for no options.
+    With `desc`: also None when the window removes no key of that problem (the library's normalisation, FaWindow in
+    csrc/fa_launch.hpp), so that such a call is the call without options in every respect -- the backward workspace included."""
+    if window is None:
+        return None
+    if not isinstance(window, (tuple, list)) or len(window) != 2 or not all(isinstance(w, int) and not isinstance(w, bool)
+                                                                           for w in window):
+        raise TypeError(f"window must be None or a pair of ints (left, right), got {window!r}")
+    left, right = int(window[0]), int(window[1])
+    if desc is not None and left >= -1 and right >= -1:
+        left_off = left == -1 or left >= desc.ql - 1
+        right_off = right == -1 or right >= desc.kl - 1 or (desc.causal != 0 and right >= 0)
+        if left_off and right_off:
+            return None
+    return FaOpts(window_left=left, window_right=right)
+
+
+def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None) -> str:
     """Name of the forward kernel the launcher picks for this problem (reporting only; csrc/nnop_debug.h)."""
-    code = load().nnop_debug_fwd_form(C.byref(desc), int(has_pair), int(has_mask))
+    opts = fa_opts(window)
+    if opts is None:
+        code = load().nnop_debug_fwd_form(C.byref(desc), int(has_pair), int(has_mask))
+    else:
+        code = load().nnop_debug_fwd_form_ex(C.byref(desc), C.byref(opts), int(has_pair), int(has_mask))
     if code < 0:
         raise ValueError(strerror(code))
     return FWD_FORMS[code]
 
 
-def bwd_kernels(desc: FaDesc, has_pair: bool = False, has_mask: bool = False):
+def bwd_kernels(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None):
     """Names of the (dK/dV, dQ) kernels the launcher picks for this problem (reporting only; csrc/nnop_debug.h)."""
-    code = load().nnop_debug_bwd_form(C.byref(desc), int(has_pair), int(has_mask))
+    opts = fa_opts(window)
+    if opts is None:
+        code = load().nnop_debug_bwd_form(C.byref(desc), int(has_pair), int(has_mask))
+    else:
+        code = load().nnop_debug_bwd_form_ex(C.byref(desc), C.byref(opts), int(has_pair), int(has_mask))
     if code < 0:
         raise ValueError(strerror(code))
     return ("fa_bwd_w64_kernel<dK/dV>" if code & 1 else "fa_bwd_dkdv_kernel", "fa_bwd_w64_kernel<dQ>" if code & 2 else "fa_bwd_dq_kernel")

@@ -142,33 +142,47 @@ def bwd_workspace_bytes(q, k, v, *, causal: bool, pair: bool = False) -> int:
     return int(f(C.byref(_desc(q, k, v, causal))))
 
 
-def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None):
+def _fwd_call(lib, opts, d, *args):
+    """nnop_fa_fwd, or nnop_fa_fwd_ex when there are per-call options (window=None issues exactly the old call)"""
+    if opts is None:
+        return lib.nnop_fa_fwd(C.byref(d), *args)
+    return lib.nnop_fa_fwd_ex(C.byref(d), C.byref(opts), *args)
+
+
+def _bwd_call(lib, opts, d, *args):
+    if opts is None:
+        return lib.nnop_fa_bwd(C.byref(d), *args)
+    return lib.nnop_fa_bwd_ex(C.byref(d), C.byref(opts), *args)
+
+
+def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
     """Raw ``nnop_fa_fwd`` into caller-owned, preallocated outputs (the C ABI's ownership model:
     the caller allocates everything).  No checks beyond the library's own; contiguous tensors only.
-    Used by bench.py so that a timed step is exactly one library call."""
+    Used by bench.py so that a timed step is exactly one library call.  ``window``: see flash_attention."""
     d = _desc(q, k, v, causal)
-    st = _lib.load().nnop_fa_fwd(C.byref(d), _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                                 _ptr(pair), _ptr(kpad_mask), _stream(q))
+    st = _fwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
+                   _ptr(pair), _ptr(kpad_mask), _stream(q))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
-def fa_bwd_into(dq, dk, dv, dpair, ws, dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None):
+def fa_bwd_into(dq, dk, dv, dpair, ws, dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
     """Raw ``nnop_fa_bwd`` into caller-owned outputs and workspace (see fa_fwd_into)."""
     d = _desc(q, k, v, causal)
-    st = _lib.load().nnop_fa_bwd(C.byref(d), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
-                                 _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                                 _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q))
+    st = _bwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
+                   _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
+                   _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
-def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None):
+def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
     """``NNop._flash_attention`` (src/attention.jl:133-177): returns ``(o, ms, ls)``.
 
-    Asynchronous on the current torch stream, like the reference's KA launch.
+    Asynchronous on the current torch stream, like the reference's KA launch.  ``window``: see flash_attention.
     """
     lib = _lib.load()
+    opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
     if k.shape[0] != q.shape[0]:
         raise NNopError(f"Batch of K `{k.shape[0]}` must be the same as of Q `{q.shape[0]}`.")
@@ -176,21 +190,24 @@ def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None):
     pair = pair.contiguous() if pair is not None else None
     kpad_mask = kpad_mask.contiguous() if kpad_mask is not None else None
     d = _desc(q, k, v, causal)
+    opts = _lib.fa_opts(window, d)            # a window that removes no key: exactly the call without one
     B, QH, QL, E = q.shape
     with _on_device(q):
         o = torch.empty_like(q)                                           # similar(q)      :166
         ms = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :167
         ls = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :168
-        st = lib.nnop_fa_fwd(C.byref(d), _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                             _ptr(pair), _ptr(kpad_mask), _stream(q))
+        st = _fwd_call(lib, opts, d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
+                       _ptr(pair), _ptr(kpad_mask), _stream(q))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
     return o, ms, ls
 
 
-def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None):
-    """``NNop.∇flash_attention`` (src/attention_bwd.jl:199-275): returns ``(dq, dk, dv, dpair|None)``."""
+def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
+    """``NNop.∇flash_attention`` (src/attention_bwd.jl:199-275): returns ``(dq, dk, dv, dpair|None)``.
+    ``window``: the forward's (see flash_attention)."""
     lib = _lib.load()
+    opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     dO, o, ms, ls = dO.contiguous(), o.contiguous(), ms.contiguous(), ls.contiguous()
@@ -210,18 +227,19 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
     pair = pair.contiguous() if pair is not None else None
     kpad_mask = kpad_mask.contiguous() if kpad_mask is not None else None
     d = _desc(q, k, v, causal)
+    opts = _lib.fa_opts(window, d)            # a window that removes no key: exactly the call without one
     with _on_device(q):
         dq = torch.empty_like(q)
         dk = torch.empty_like(k)
         dv = torch.empty_like(v)
         dpair = torch.empty_like(pair) if pair is not None else None
         nbytes = small = int(lib.nnop_fa_bwd_workspace_bytes(C.byref(d)))
-        if nbytes != 0 and pair is not None:
+        if nbytes != 0 and pair is not None and opts is None:
             # staged pair-bias path: two head-major bias-sized scratch matrices on top (the library returns the small size
             # where that path does not exist: plain-HIP embedding dims, too many heads for its LDS block)
             nbytes = max(nbytes, int(lib.nnop_fa_bwd_workspace_bytes_pair(C.byref(d))))
         if nbytes == 0:
-            st = lib.nnop_fa_bwd(C.byref(d), *([C.c_void_p(0)] * 13), C.c_void_p(0), 0, C.c_void_p(0))
+            st = _bwd_call(lib, opts, d, *([C.c_void_p(0)] * 13), C.c_void_p(0), 0, C.c_void_p(0))
             _raise_status(st, q, k, v)
         try:
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
@@ -230,9 +248,9 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
                 raise
             nbytes = small                     # no room for the scratch: the direct (element-wise) pair path needs none
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
-        st = lib.nnop_fa_bwd(C.byref(d), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
-                             _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                             _ptr(ws), C.c_size_t(nbytes), _stream(q))
+        st = _bwd_call(lib, opts, d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
+                       _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
+                       _ptr(ws), C.c_size_t(nbytes), _stream(q))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
     return dq, dk, dv, dpair
@@ -244,11 +262,11 @@ class _FlashAttentionFn(torch.autograd.Function):
     no tangent for kpad_mask."""
 
     @staticmethod
-    def forward(ctx, q, k, v, pair, kpad_mask, causal):
-        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask)
+    def forward(ctx, q, k, v, pair, kpad_mask, causal, window=None):
+        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window)
         ctx.save_for_backward(o, ms, ls, q, k, v, pair if pair is not None else torch.empty(0),
                               kpad_mask if kpad_mask is not None else torch.empty(0))
-        ctx.has_pair, ctx.has_mask, ctx.causal = pair is not None, kpad_mask is not None, bool(causal)
+        ctx.has_pair, ctx.has_mask, ctx.causal, ctx.window = pair is not None, kpad_mask is not None, bool(causal), window
         return o
 
     @staticmethod
@@ -256,15 +274,21 @@ class _FlashAttentionFn(torch.autograd.Function):
         o, ms, ls, q, k, v, pair, mask = ctx.saved_tensors
         dq, dk, dv, dpair = grad_flash_attention(
             dO, o, ms, ls, q, k, v, pair if ctx.has_pair else None,
-            causal=ctx.causal, kpad_mask=mask if ctx.has_mask else None)
-        return dq, dk, dv, dpair, None, None
+            causal=ctx.causal, kpad_mask=mask if ctx.has_mask else None, window=ctx.window)
+        return dq, dk, dv, dpair, None, None, None
 
 
-def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None):
+def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
     """``NNop.flash_attention(q, k, v, pair=nothing; causal, kpad_mask=nothing)``
     (src/attention_crc.jl:4-14).  ``causal`` is a required keyword, as in the reference.
-    Returns ``o``; differentiable w.r.t. q, k, v, pair through the rrule above."""
+    Returns ``o``; differentiable w.r.t. q, k, v, pair through the rrule above.
+
+    ``window=(left, right)``: sliding-window (local) attention in flash-attn's ``window_size`` convention -- query i
+    sees key j only if ``i - left <= j <= i + right`` (on top of ``causal`` and ``kpad_mask``); ``-1`` leaves a side
+    unbounded.  Top-left aligned (query i lines up with key i) whatever QL and KL are.  ``None``: no window."""
+    if window is not None:
+        window = tuple(window)
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (q, k, v, pair)):
-        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal))
-    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask)[0]
+        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal), window)
+    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window)[0]

@@ -66,6 +66,8 @@ struct BwdParams {
     int   persist_hx = 0;   // persistent form: heads of the column axis per XCD when they divide by 8 (fa_fwd.hpp), else 0
     int   causal_alt = 0;   // fa_bwd_dkdv_kernel / fa_bwd_dq_kernel, causal: g > 0 -- every second run of g consecutive blocks of an XCD's dispatch order runs its blocks the other way round (fa_launch.hpp causal_alt_run)
     int   persist = 0;   // fa_bwd_w64_kernel: blocks per workgroup of the persistent form (grid = 256 workgroups), 0 = one block per workgroup
+    int   win_left = -1;    // the WIN = true kernels and the plain-HIP ones: sliding window (FaWindow, normalised), -1 = unbounded side
+    int   win_right = -1;   // (behind the older fields: their kernel-argument offsets stay where they were)
 };
 
 // An fp32 row constant as three 16-bit terms (hi, mid, lo, 0 ...) whose sum is the value to ~24 bits: the form in which the dK/dV
@@ -233,9 +235,12 @@ constexpr int fa_bwd_dkdv_lds_bytes() {
 }
 
 // MODE 0 plain / 1 masked (causal, key padding) / 2 masked + pair bias and dpair  (as in fa_fwd.hpp)
-template <typename T, int E, int NW, int BQ, int MODE>
+// WIN (MODE 1 / 2): sliding window p.win_left / p.win_right -- the q tiles of a key block are bounded by it and the blocks that cross
+// a window edge take the per-element select.  WIN = false compiles to the code without a window.
+template <typename T, int E, int NW, int BQ, int MODE, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void fa_bwd_dkdv_kernel(const BwdParams p) {
     constexpr bool kGeneral = MODE != 0;
+    static_assert(!WIN || (MODE == 1 || MODE == 2), "the window runs in the masked modes (direct pair path)");
     constexpr bool kPair = MODE >= 2;
     constexpr bool kStaged = MODE == 3;          // pair bias through head-major scratch + LDS tiles (pair_tile.hpp)
     using frag_t = typename Elem<T>::frag;
@@ -322,7 +327,17 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
     const int n_qt = (p.QL + BQ - 1) / BQ;
     int qt0 = 0;
     if (kGeneral && p.causal) qt0 = k0wg / BQ;           // queries < first key of the block see none of it
-    const int nqt = n_qt > qt0 ? n_qt - qt0 : 0;
+    int qt_end = n_qt;
+    if constexpr (WIN) {
+        // queries [k_first - right, k_last + left] see some key of the block
+        if (p.win_right >= 0 && k0wg - p.win_right > 0 && (k0wg - p.win_right) / BQ > qt0) qt0 = (k0wg - p.win_right) / BQ;
+        if (p.win_left >= 0) {
+            const int k_last = k0wg + 32 * NW - 1 < p.KL - 1 ? k0wg + 32 * NW - 1 : p.KL - 1;
+            const long long q_hi = (long long)k_last + p.win_left;
+            if (q_hi / BQ + 1 < qt_end) qt_end = (int)(q_hi / BQ + 1);
+        }
+    }
+    const int nqt = qt_end > qt0 ? qt_end - qt0 : 0;
     const int n_it = nqt * rep;
 
     Stager<T, E, BQ, NT> sq, sdo;
@@ -399,6 +414,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             const int q0 = qt * BQ + 32 * qb;
             if (q0 >= p.QL) continue;
             if (kGeneral && p.causal && q0 + 31 < kw0) continue;       // block entirely above the diagonal
+            if constexpr (WIN) {                                           // block entirely outside the window
+                if (p.win_right >= 0 && q0 + 31 + p.win_right < kw0) continue;
+                if (p.win_left >= 0 && q0 - p.win_left > kw0 + 31) continue;
+            }
 
             typename PairTile<T>::Regs pregs;                              // kStaged: the bias tile, fetched ahead of the MFMAs
             if constexpr (kStaged) {
@@ -426,7 +445,11 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             }
 
             // P = exp2(c*S'), dS = P*dP'   (rows = queries in registers, key on the lane)
-            const bool diag = kGeneral && p.causal && (q0 < kw0 + 31);
+            bool diag = kGeneral && p.causal && (q0 < kw0 + 31);
+            if constexpr (WIN) {                                           // ... or crossing a window edge
+                if (p.win_right >= 0 && q0 + p.win_right < kw0 + 31) diag = true;
+                if (p.win_left >= 0 && q0 + 31 - p.win_left > kw0) diag = true;
+            }
             // pair / dpair [B][KL][QL][QH]: one 64-bit base per (q-block, lane); rows are QH elements apart
             // (dpair is written by the dQ kernel, where the lane axis is the tensor's contiguous direction)
             const T* pbase = nullptr;
@@ -454,7 +477,17 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                         x += to_f32(pbase[lr * p.QH]) * kLog2e;
                     }
                     float pr = fast_exp2(x);
-                    if constexpr (decltype(masked)::value) pr = (!diag || q0 + lrow >= key) ? pr : 0.f;
+                    if constexpr (decltype(masked)::value) {
+                        if constexpr (WIN) {
+                            const int qq = q0 + lrow;
+                            bool ok = !p.causal || qq >= key;
+                            if (p.win_right >= 0) ok = ok && qq + p.win_right >= key;
+                            if (p.win_left >= 0) ok = ok && qq - p.win_left <= key;
+                            pr = (!diag || ok) ? pr : 0.f;
+                        } else {
+                            pr = (!diag || q0 + lrow >= key) ? pr : 0.f;
+                        }
+                    }
                     s[i] = pr;
                     ds[i] = pr * dp[i];
                 }
@@ -532,9 +565,11 @@ constexpr int fa_bwd_dq_lds_bytes() {
            nbuf * (BwdImgs<T, E>::both(BK) + RowImg<T, E>::bytes(BK)) + 8 * kMaxMaskTilesBwd;   // + validity words
 }
 
-template <typename T, int E, int NW, int BK, int MODE>
+// WIN (MODE 1 / 2): sliding window -- the key tiles are bounded as in the forward; `need_mask` covers the window edges.
+template <typename T, int E, int NW, int BK, int MODE, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void fa_bwd_dq_kernel(const BwdParams p) {
     constexpr bool kGeneral = MODE != 0;
+    static_assert(!WIN || (MODE == 1 || MODE == 2), "the window runs in the masked modes (direct pair path)");
     constexpr bool kPair = MODE >= 2;
     constexpr bool kStaged = MODE == 3;          // pair bias / dS through head-major scratch + LDS tiles (pair_tile.hpp)
     using frag_t = typename Elem<T>::frag;
@@ -585,6 +620,16 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
         if (q_last > p.QL - 1) q_last = p.QL - 1;
         const int t_c = q_last / BK + 1;
         if (t_c < n_tiles) n_tiles = t_c;
+    }
+    int t_first = 0;                                           // WIN: first kv tile some query of the workgroup sees
+    if constexpr (WIN) {
+        int q_last = q0wg + 32 * NW - 1;
+        if (q_last > p.QL - 1) q_last = p.QL - 1;
+        if (p.win_right >= 0) {
+            const long long t_r = ((long long)q_last + p.win_right) / BK + 1;
+            if (t_r < n_tiles) n_tiles = (int)t_r;
+        }
+        if (p.win_left >= 0 && q0wg - p.win_left > 0) t_first = (q0wg - p.win_left) / BK;
     }
 
     if constexpr (kGeneral) {
@@ -640,9 +685,9 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
         for (int i = 0; i < 16; ++i) dqa[eb][i] = 0.f;
     const int cbase = Col::lane_base(lane);
 
-    if (n_tiles > 0) {
-        stage_load(0);
-        stage_write(bufs);
+    if (n_tiles > t_first) {
+        stage_load(t_first);
+        stage_write(bufs + (t_first & 1) * BUF);
     }
     if constexpr (kQRegs) {
 #pragma unroll
@@ -654,7 +699,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
     }
     __syncthreads();
 
-    for (int t = 0; t < n_tiles; ++t) {
+    for (int t = t_first; t < n_tiles; ++t) {
         char* cur = bufs + (t & 1) * BUF;
         char* nxt = bufs + ((t + 1) & 1) * BUF;
         const bool more = t + 1 < n_tiles;
@@ -665,6 +710,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
         uint64_t valid = ~0ull;
         if constexpr (kGeneral) {
             if (p.causal && k0 > q0w + 31) skip = true;
+            if constexpr (WIN) {                                   // tile outside the window of every row of the wave
+                if (p.win_right >= 0 && k0 > q0w + 31 + p.win_right) skip = true;
+                if (p.win_left >= 0 && k0 + BK - 1 < q0w - p.win_left) skip = true;
+            }
             if (BK < 64) valid = (1ull << BK) - 1ull;
             if (k0 + BK > p.KL) valid &= (p.KL - k0 >= 64) ? ~0ull : ((1ull << (p.KL - k0)) - 1ull);
             if (mp) {
@@ -680,6 +729,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             if (valid == 0ull) skip = true;
             need_mask = (valid != ((BK < 64) ? ((1ull << BK) - 1ull) : ~0ull)) ||
                         (p.causal && k0 + BK - 1 > q0w) || (kPair && !kStaged);
+            if constexpr (WIN) {                                   // tile crossing a window edge of some row
+                if (p.win_right >= 0 && k0 + BK - 1 > q0w + p.win_right) need_mask = true;
+                if (p.win_left >= 0 && k0 < q0w + 31 - p.win_left) need_mask = true;
+            }
         }
 
         if (!skip) {
@@ -737,6 +790,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                             const int lr = (i & 3) + 8 * (i >> 2);
                             ok = (w >> lr) & 1u;
                             if (p.causal) ok = ok && (lr <= lim);
+                            if constexpr (WIN) {                   // key k0 + 32 kb + 4 h + lr vs query qi
+                                if (p.win_right >= 0) ok = ok && (lr <= lim + p.win_right);
+                                if (p.win_left >= 0) ok = ok && (lr >= lim - p.win_left);
+                            }
                             if constexpr (kPair && !kStaged) {
                                 int kl = 32 * kb + lr + 4 * h;
                                 kl = kl < kmax ? kl : kmax;

@@ -36,11 +36,11 @@ static inline int bwd_causal_alt(const nnop_fa_desc& d, long long n_wg, long lon
     return causal_alt_run(d.causal != 0, n_wg, cols, rep, n_blk);
 }
 
-template <typename T, int E, int NW, int BQ, int MODE>
+template <typename T, int E, int NW, int BQ, int MODE, bool WIN = false>
 static int launch_dkdv(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
     constexpr int lds = fa_bwd_dkdv_lds_bytes<T, E, NW, BQ, MODE>() + (MODE == 3 ? NW * PairTile<T>::kBytes : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fa_bwd_dkdv_kernel<T, E, NW, BQ, MODE>;
+    auto kern = fa_bwd_dkdv_kernel<T, E, NW, BQ, MODE, WIN>;
     static unsigned long long lds_done = 0;
     if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     BwdParams pk = p;
@@ -49,16 +49,16 @@ static int launch_dkdv(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s)
     if (n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     pk.n_wg = (int)n_wg;
     if (n_wg * fa_bwd_split<T, E>() > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    pk.causal_alt = bwd_causal_alt(d, n_wg, (long long)d.kh * d.batch, 1, pk.n_blk, MODE >= 2);
+    pk.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.kh * d.batch, 1, pk.n_blk, MODE >= 2);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg * fa_bwd_split<T, E>())), dim3(NW * 64), lds, s, pk);   // (fp32 E = 256: every block once per column slice)
     return NNOP_OK;
 }
 
-template <typename T, int E, int NW, int BK, int MODE>
+template <typename T, int E, int NW, int BK, int MODE, bool WIN = false>
 static int launch_dq(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
     constexpr int lds = fa_bwd_dq_lds_bytes<T, E, NW, BK, MODE>() + (MODE == 3 ? NW * PairTile<T>::kBytes : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fa_bwd_dq_kernel<T, E, NW, BK, MODE>;
+    auto kern = fa_bwd_dq_kernel<T, E, NW, BK, MODE, WIN>;
     static unsigned long long lds_done = 0;
     if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     BwdParams pq = p;
@@ -67,7 +67,7 @@ static int launch_dq(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
     if (n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     pq.n_wg = (int)n_wg;
     if (n_wg * fa_bwd_split<T, E>() > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    pq.causal_alt = bwd_causal_alt(d, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, pq.n_blk, MODE >= 2);
+    pq.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, pq.n_blk, MODE >= 2);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg * fa_bwd_split<T, E>())), dim3(NW * 64), lds, s, pq);
     return NNOP_OK;
 }
@@ -135,15 +135,15 @@ static inline bool bwd_w64_narrow(const nnop_fa_desc& d, int kind) {
     return small_grid_prefers_32_row_waves(len, (long long)hd * d.batch, d.causal != 0);
 }
 // bit 0: dK/dV runs fa_bwd_w64_kernel, bit 1: dQ does (knob kTuneBwdW64: 0 never, 1 both, 2 dK/dV only, 3 dQ only, 4 both with the
-// preprocess launch kept, auto = both)
-static inline int bwd_w64_forms(const nnop_fa_desc& d, bool has_pair, bool ws_aligned16) {
-    if (has_pair) return 0;
+// preprocess launch kept, auto = both).  Never with a sliding window (fa_bwd.hpp WIN only).
+static inline int bwd_w64_forms(const nnop_fa_desc& d, bool has_pair, bool ws_aligned16, bool windowed = false) {
+    if (has_pair || windowed) return 0;
     const int t = tune_get(kTuneBwdW64);
     const bool want_kv = t < 0 || t == 1 || t == 2 || t == 4, want_q = t < 0 || t == 1 || t == 3 || t == 4;
     return ((want_kv && ws_aligned16 && bwd_w64_ok(d, kBwdDKDV)) ? 1 : 0) | ((want_q && bwd_w64_ok(d, kBwdDQ)) ? 2 : 0);
 }
 
-template <typename T, int E, int MODE>
+template <typename T, int E, int MODE, bool WIN = false>
 static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) {
     using C = BwdCfg<T, E>;
     BwdParams p;
@@ -161,6 +161,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     p.fused = 0;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
+    if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
     p.scale = (float)(1.0 / sqrt((double)E));
     p.n_blk = 0; p.n_wg = 0;
     p.pair_a = nullptr; p.dpair_s = nullptr;
@@ -180,7 +181,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     // measurement only (kTuneBwdStages, bench.py's per-kernel times): run a subset of the passes -- 1 preprocess, 2 dK/dV, 4 dQ
     const int stages = tune_get(kTuneBwdStages) < 0 ? 7 : tune_get(kTuneBwdStages);
     // the one-wave-per-SIMD form (fa_bwd_w64.hpp): 16-bit, E = 64 / 128, plain / masked modes
-    const int w64_forms = MODE <= 1 ? bwd_w64_forms(d, false, p.rcf != nullptr) : 0;
+    const int w64_forms = (MODE <= 1 && !WIN) ? bwd_w64_forms(d, false, p.rcf != nullptr) : 0;
     const bool w64_kv = (w64_forms & 1) != 0, w64_q = (w64_forms & 2) != 0;
     // Both passes in that form: no preprocess launch -- the dQ kernel computes the row constants of its own rows and leaves them
     // (fragment form) for the dK/dV kernel, which therefore runs BEHIND it.  (kTuneBwdW64 = 4: both passes, preprocess kept: A/B)
@@ -203,6 +204,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     const int big_thr = big_tune >= 0 ? big_tune : (d.causal ? 512 : 256);
     // 3. dK, dV
     auto run_dkdv = [&]() -> int {
+        if constexpr (WIN) return launch_dkdv<T, E, C::NW_KV, C::BQ, MODE, true>(d, p, s);     // the one windowed shape
         int st = NNOP_OK;
         bool done = false;
         if constexpr (MODE <= 1 && sizeof(T) == 2 && (E == 64 || E == 128 || E == 256)) {
@@ -229,6 +231,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     };
     // 4. dQ
     auto run_dq = [&]() -> int {
+        if constexpr (WIN) return launch_dq<T, E, C::NW_Q, C::BK, MODE, true>(d, p, s);
         int st = NNOP_OK;
         bool done = false;
         if constexpr (MODE <= 1 && sizeof(T) == 2 && (E == 64 || E == 128 || E == 256)) {
@@ -280,6 +283,15 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
 
 template <typename T, int E>
 static int launch_bwd_e(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) {
+    if (a.win.on()) {
+        // sliding window: the WIN bodies of fa_bwd.hpp; with a pair bias always the direct path (MODE 2), never the staged scratch
+        if constexpr (sizeof(T) == 4 && E == 256) {
+            if (a.pair) return NNOP_ERR_EMB_UNSUPPORTED;
+            return launch_bwd_cfg<T, E, 1, true>(d, a, s);
+        } else {
+            return a.pair ? launch_bwd_cfg<T, E, 2, true>(d, a, s) : launch_bwd_cfg<T, E, 1, true>(d, a, s);
+        }
+    }
     if constexpr (sizeof(T) == 4 && E == 256) {
         if (a.pair) return NNOP_ERR_EMB_UNSUPPORTED;             // (launch_bwd sends fp32 E = 256 with a pair bias to the plain-HIP kernels)
         return (d.causal || a.kpad) ? launch_bwd_cfg<T, E, 1>(d, a, s) : launch_bwd_cfg<T, E, 0>(d, a, s);
@@ -308,6 +320,7 @@ template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const
     p.delta = p.nl + n_rows;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
+    p.win_left = a.win.left; p.win_right = a.win.right;
     p.scale = (float)(1.0 / sqrt((double)d.emb));
     p.n_blk = 0; p.n_wg = 0;
     p.pair_a = nullptr; p.dpair_s = nullptr; p.QLp = p.KLp = 0;

@@ -91,6 +91,10 @@ struct FwdParams {
     int   persist = 0;       // fa_fwd_w64_kernel: blocks per workgroup of the persistent form (grid = 256 workgroups), 0 = one block per workgroup
     int   persist_asc = 0;   // persistent form: q-blocks of a column in ASCENDING order (light blocks first), see fwd_persist_plan
     int   causal_alt = 0;    // fa_fwd_kernel, causal: g > 0 -- every second run of g consecutive blocks of an XCD's dispatch order (whole columns) runs its q-blocks ascending (launch_fwd_cfg)
+    // fa_fwd_kernel<..., WIN = true> and fa_fwd_generic_kernel: sliding window (FaWindow, normalised), -1 = unbounded side.  Behind
+    // the older fields, so that their kernel-argument offsets stay where they were.
+    int   win_left = -1;
+    int   win_right = -1;
 #ifdef NNOP_DEV_BUILD
     int   stagger = 0;       // experiment: s_sleep units for the odd co-resident workgroup (0 = off)
 #endif
@@ -99,13 +103,18 @@ struct FwdParams {
 // MODE 0: plain   -- KL % BK == 0, no causal, no kpad, no pair: every logit is live
 // MODE 1: masked  -- causal and/or key padding and/or ragged KL
 // MODE 2: pair    -- masked + additive pair bias
-template <typename T, int E, int NW, int BK, int MODE, int QB>
+// WIN (MODE 1 / 2 only): sliding window p.win_left / p.win_right.  The workgroup walks kv tiles [t_lo, t_hi) only; loop indices
+// are RELATIVE to t_lo (tile t of the walk is kv tile t0 + t), each wave computes only its own live tiles [w_lo, n_live), one
+// tile per interval (no software pipeline, see kPipe), and takes the per-element select only on tiles that cross a window
+// edge, the diagonal, KL or a key-padding word (tile_needs_mask).  WIN = false compiles to the code without a window.
+template <typename T, int E, int NW, int BK, int MODE, int QB, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) ? 1 : 2) void fa_fwd_kernel(const FwdParams p) {
     using frag_t = typename Elem<T>::frag;
     using KImg   = RowImg<T, E>;
     using VImg   = ColImg<T, E>;
     constexpr bool kGeneral = MODE != 0;
     constexpr bool kPair = MODE == 2;
+    static_assert(!WIN || kGeneral, "the window runs in the masked modes");
     constexpr int NT  = NW * 64;
     constexpr int KS  = E / 16;                 // contraction steps of Q K^T
     constexpr int KB  = BK / 32;                // 32-key blocks per kv tile
@@ -123,7 +132,10 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
     // kDeep    : HBM loads run two intervals ahead of the LDS writes (two register sets)
     // kMfmaSum : row sums on the matrix pipe
     constexpr bool k16 = sizeof(T) == 2;
-    constexpr bool kPipe = k16 && (E <= 64 || MODE == 0);      // E = 128 masked, pipelined: 716 B/lane of spills, 2x slower
+    // E = 128 masked, pipelined: 716 B/lane of spills, 2x slower.  WIN: one tile per interval as well -- the pipelined windowed body
+    // (a general run, the plain run, a general run) measured slower at bf16 E = 64 L16384 H8 causal even once spill-free: window
+    // (1023, 0) 80.7 vs 73.2 us, (255, 0) 47.2 vs 40.3 us
+    constexpr bool kPipe = k16 && (E <= 64 || MODE == 0) && !WIN;
     constexpr bool kPrefetch = NNOP_V_PREFETCH && k16 && (QB == 2 ? E <= 64 : (MODE == 0 && E <= 64));
     constexpr int  PFK = kPrefetch ? (NKF <= 8 ? NKF : 8) : 0;
     constexpr int  PFV = kPrefetch ? (NVF <= 8 ? NVF : 8) : 0;
@@ -173,12 +185,23 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
 
     // ---- number of kv tiles this workgroup walks ---------------------------------------
     int n_tiles = (p.KL + BK - 1) / BK;
+    int t0 = 0;                                                // WIN: first kv tile of the walk (loop indices below are relative to it)
     if constexpr (kGeneral) {
         if (p.causal) {
             int q_last = qblk * (WROWS * NW) + WROWS * NW - 1;
             if (q_last > p.QL - 1) q_last = p.QL - 1;
             const int t_c = q_last / BK + 1;                   // keys <= q_last
             if (t_c < n_tiles) n_tiles = t_c;
+        }
+        if constexpr (WIN) {
+            const int q_first = qblk * (WROWS * NW);
+            int q_last = q_first + WROWS * NW - 1;
+            if (q_last > p.QL - 1) q_last = p.QL - 1;
+            if (p.win_right >= 0) {
+                const long long t_r = ((long long)q_last + p.win_right) / BK + 1;     // keys <= q_last + right
+                if (t_r < n_tiles) n_tiles = (int)t_r;
+            }
+            if (p.win_left >= 0 && q_first - p.win_left > 0) t0 = (q_first - p.win_left) / BK;   // keys >= q_first - left
         }
         if (mp) {
             // variable sequence length: one pass over the mask row builds the per-64-key validity words in LDS and
@@ -197,6 +220,21 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
         const int t_w = (q0w + WROWS - 1) / BK + 1;
         if (t_w < n_live) n_live = t_w;
     }
+    int w_lo = 0;                                              // WIN: first live tile of this wave (relative)
+    if constexpr (WIN) {
+        const int wq1 = q0w + WROWS - 1;                       // (rows past QL only make the bounds wider)
+        if (p.win_right >= 0) {
+            const long long t_w = ((long long)wq1 + p.win_right) / BK + 1;
+            if (t_w < n_live) n_live = (int)t_w;
+        }
+        int lo = 0;                                            // first tile with a key some row of the wave sees
+        if (p.win_left >= 0 && q0w - p.win_left > 0) lo = (q0w - p.win_left) / BK;
+        // relative to t0
+        n_tiles = n_tiles > t0 ? n_tiles - t0 : 0;
+        n_live = n_live > t0 ? n_live - t0 : 0;
+        if (n_live > n_tiles) n_live = n_tiles;
+        w_lo = lo > t0 ? lo - t0 : 0;
+    }
 
     // Leading run of tiles that are PLAIN for this wave: fully inside KL, every key valid, not clipped by the causal
     // diagonal of the wave's first row, live.  The pipelined loop below runs the plain-mode interval (one basic block,
@@ -205,7 +243,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
     // alone is 1.45x slower per tile than plain mode at E = 64).  Every interval holds exactly one barrier, so waves of
     // a workgroup may switch at different tiles.
     int first_special = n_live;
-    if constexpr (kGeneral) {
+    if constexpr (kGeneral && !WIN) {
         if (p.causal) {
             const int t_c = (q0w + 1) / BK;                   // first tile the wave's first row does not fully see
             if (t_c < first_special) first_special = t_c;
@@ -248,6 +286,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
     //   one interval further ahead than the LDS writes (two register sets).
     Stager<T, E, BK, NT> sk0, sv0, sk1, sv1;
     auto stage = [&](Stager<T, E, BK, NT>& st, const char* base, int t) {
+        if constexpr (WIN) t += t0;
         if constexpr (kGeneral) st.load(base + (size_t)t * ((size_t)BK * E * sizeof(T)), p.KL - t * BK, tid);
         else st.load_full(base + (size_t)t * ((size_t)BK * E * sizeof(T)), tid);
     };
@@ -334,6 +373,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
     };
     // wave-uniform: which keys of tile t are valid (bounds + key padding); does it need masking
     auto tile_valid = [&](int t) -> uint64_t {
+        if constexpr (WIN) t += t0;
         uint64_t valid = kFull;
         if constexpr (kGeneral) {
             const int k0 = t * BK;
@@ -351,12 +391,22 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
         return valid;
     };
     auto tile_needs_mask = [&](int t, uint64_t valid) {
+        if constexpr (WIN) {
+            // masked unless every row of the wave sees every valid key of the tile (both window edges, the causal rule)
+            t += t0;
+            if (valid != kFull) return true;
+            if (p.causal && t * BK + BK - 1 > q0w) return true;
+            if (p.win_right >= 0 && (long long)t * BK + BK - 1 > (long long)q0w + p.win_right) return true;
+            if (p.win_left >= 0 && t * BK < q0w + WROWS - 1 - p.win_left) return true;
+            return false;
+        }
         return kGeneral && (valid != kFull || (p.causal && t * BK + BK - 1 > q0w));
     };
     // mask (-> -inf) / bias tile t of query block z in place and return its row max in log2 units (both halves).
     // Plain / masked: logits stay in raw units; kPair: they become log2 units (s*c2 + pair*log2e).
     auto finish_x = [&](auto masked, int z, f32x16 (&s)[KB], int t, uint64_t valid) -> float {
         constexpr bool MASKED = decltype(masked)::value;
+        if constexpr (WIN) t += t0;
         const int k0 = t * BK;
         float mxp[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // 4 independent chains
         if constexpr (MASKED || kPair) {
@@ -381,6 +431,10 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
                     if constexpr (MASKED) {
                         ok = (w >> lr) & 1u;
                         if (p.causal) ok = ok && (lr <= lim);
+                        if constexpr (WIN) {                                 // key k0 + 32 kb + 4 h + lr vs query qi[z]
+                            if (p.win_right >= 0) ok = ok && (lr <= lim + p.win_right);
+                            if (p.win_left >= 0) ok = ok && (lr >= lim - p.win_left);
+                        }
                     }
                     float x = s[kb][i];
                     if constexpr (kPair) {
@@ -511,7 +565,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
         for (int t = 0; t < n_tiles; ++t) {
             const bool more1 = t + 1 < n_tiles;
             if (more1) { stage(sk0, kp, t + 1); stage(sv0, vp, t + 1); }
-            if (t < n_live) {
+            if (t < n_live && (!WIN || t >= w_lo)) {
                 f32x16 sc[QB][KB];
                 float mxr[QB];
                 frag_t kfr[PFK > 0 ? PFK : 1], vfr[PFV > 0 ? PFV : 1];

@@ -26,14 +26,14 @@ static inline int dev_env_int(const char* name, int dflt) {
 }
 #endif
 
-template <typename T, int E, int NW, int MODE, int QB>
+template <typename T, int E, int NW, int MODE, int QB, bool WIN = false>
 static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     // 64-key tiles, except the E = 128 pair-bias body (register budget) and fp32 E = 128
     // (LDS: 2 x (K + V) x 64 keys x 512 B = 128 KiB would leave one workgroup per CU)
     constexpr int BK = (E >= 256 || (E >= 128 && (MODE == 2 || sizeof(T) == 4))) ? 32 : 64;
     constexpr int lds = fa_fwd_lds_bytes<T, E, BK>();
     static_assert(lds <= 160 * 1024, "LDS budget (160 KiB per CU on gfx950)");
-    auto kern = fa_fwd_kernel<T, E, NW, BK, MODE, QB>;
+    auto kern = fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
     static unsigned long long lds_done = 0;
     if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
@@ -51,8 +51,10 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     // profiles/r04/causal_alt.log): fp32 E64 L4096 H4 B4 545.6 -> 319.6 us, fp32 E32 301 -> 180, fp32 E16 233 -> 142, bf16 E16 69.8 -> 53.0,
     // fp32 E64 L2048 H8 B8 (4 rounds) 473 -> 428; GQA at 4 rounds -5 %, 8 rounds and more -12 % (the rule stops before).  Where ONE workgroup
     // fills a CU there is nothing to pair (E = 128 with 8 waves; fp32 E = 128 with 4 waves fits two).
-    p.causal_alt = (MODE != 2 && (E <= 64 || (E == 128 && sizeof(T) == 4 && NW == 4)))
+    // (a window: every block walks about the same number of tiles -- nothing to pair)
+    p.causal_alt = (!WIN && MODE != 2 && (E <= 64 || (E == 128 && sizeof(T) == 4 && NW == 4)))
                        ? causal_alt_run(d.causal != 0, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, p.n_qblk) : 0;
+    if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
     int lds_launch = lds;
 #ifdef NNOP_DEV_BUILD
     // experiments (make DEV=1 only): de-phase co-resident workgroups; pad LDS to limit workgroups per CU
@@ -182,9 +184,9 @@ static int launch_fwd_mode(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t 
 }
 
 // The launcher's choice of kernel form, as a plain function of the descriptor (also reported through nnop_debug_fwd_form).
-//   mode: 0 plain (every logit live), 1 masked (causal / key padding / ragged KL), 2 + pair bias
-static inline int fwd_mode(const nnop_fa_desc& d, bool has_pair, bool has_mask) {
-    return has_pair ? 2 : ((d.causal || has_mask || (d.kl % 64) != 0) ? 1 : 0);
+//   mode: 0 plain (every logit live), 1 masked (causal / key padding / ragged KL / sliding window), 2 + pair bias
+static inline int fwd_mode(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed = false) {
+    return has_pair ? 2 : ((d.causal || has_mask || windowed || (d.kl % 64) != 0) ? 1 : 0);
 }
 // Rows per wave of the two-waves-per-SIMD form at E = 64: 64 (NZ = 2, 256-row workgroups), or 32 (NZ = 1: twice the workgroups) where the
 // 256-row blocks leave CUs idle (small_grid_prefers_32_row_waves, fa_launch.hpp; L1024 H8 B4: 19.8 -> 14.0 us; L2048 H4 B4: 30.9 -> 21.4 us;
@@ -195,11 +197,13 @@ static inline int fwd_duo_nz(const nnop_fa_desc& d) {
     if (duo == 3) return 1;
     return small_grid_prefers_32_row_waves(d.ql, (long long)d.qh * d.batch, d.causal != 0) ? 1 : 2;
 }
-static inline int fwd_form_of(const nnop_fa_desc& d, int mode) {
+static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = false) {
     const bool b16 = d.dtype != NNOP_F32;
     const int E = d.emb;
     // the early exits of launch_fwd: embedding dims outside the tiled set (16-bit E = 256 runs the 32-row tiled kernel)
     if (E != 256 && emb_generic(E)) return kFormGeneric;
+    // a sliding window (FaWindow::on) exists in the 32-row kernel only (fa_fwd.hpp WIN), not in the duo / w64 / split forms
+    if (windowed) return kFormRow32;
     const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
     if (b16 && E == 256) {
         // E = 256: the 64-row form with two 128-column halves of O per block (spill-free; the 32-row form spills 62-152 registers
@@ -268,8 +272,13 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode) {
 
 template <typename T, int E>
 static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
-    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr);
-    const int form = fwd_form_of(d, mode);
+    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr, a.win.on());
+    const int form = fwd_form_of(d, mode, a.win.on());
+    if (a.win.on()) {
+        // sliding window: the 32-row kernel's WIN body, 4 waves (128-row workgroups: a block's rows span less of the window, and a
+        // windowed grid has as many blocks as the causal one)
+        return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true>(d, a, s);
+    }
     // Workgroup shape of the 32-row form: 8 waves x 32 rows (256-row workgroups) when that still yields >= one
     // workgroup per CU, else 4 waves x 32 rows so that small problems spread over more CUs.
     const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
@@ -346,6 +355,7 @@ template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
+    p.win_left = a.win.left; p.win_right = a.win.right;
     p.n_qblk = 0; p.n_wg = 0;
     p.scale = (float)(1.0 / sqrt((double)d.emb));
     const long long n_rows = (long long)d.batch * d.qh * d.ql;

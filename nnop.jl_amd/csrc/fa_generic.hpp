@@ -3,7 +3,8 @@
 // The reference accepts any power-of-two embedding dim whose tiles fit shared memory (src/attention.jl:143,193-205); the tiled
 // kernels of this library exist for E in {16, 32, 64, 128}.  So that the boundary never rejects what the reference accepts,
 // every other power of two from 1 to 512 runs here: plain HIP, one wave per row, fp32 arithmetic, no matrix cores, the same
-// contract (causal top-left aligned, key padding, grouped-query heads, pair bias and dpair, ragged lengths, residuals ms / ls
+// contract (causal top-left aligned, sliding window (runtime bounds p.win_left / p.win_right), key padding, grouped-query
+// heads, pair bias and dpair, ragged lengths, residuals ms / ls
 // per src/attention.jl:128-129, a row without a visible key gives NaN in o and zero gradients).  Correctness path, not a
 // fast one (1-7 TFLOP/s).  E = 256 does NOT come here in the 16-bit types (the one-wave-per-SIMD kernels run it, DESIGN.md
 // section 6) nor for the fp32 FORWARD (the 32-row tiled kernel); the fp32 E = 256 backward does.
@@ -38,6 +39,13 @@ template <typename T> NNOP_DEV float dot_lds(const float* a, const T* __restrict
     return s;
 }
 
+// keys [kbeg, kend) that query qi sees by the causal rule and the window (key padding aside)
+NNOP_DEV void generic_key_range(int causal, int wl, int wr, int qi, int KL, int& kbeg, int& kend) {
+    kend = causal ? (qi + 1 < KL ? qi + 1 : KL) : KL;
+    if (wr >= 0 && (long long)qi + wr + 1 < kend) kend = qi + wr + 1;
+    kbeg = (wl >= 0 && qi - wl > 0) ? qi - wl : 0;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void fa_fwd_generic_kernel(const FwdParams p, int E, long long n_rows) {
     __shared__ float qs_all[4][kGenericMaxE];
@@ -55,11 +63,12 @@ __global__ __launch_bounds__(256) void fa_fwd_generic_kernel(const FwdParams p, 
     const T* kb = (const T*)p.k + ((size_t)(b * p.KH + kvh) * p.KL) * E;
     const T* vb = (const T*)p.v + ((size_t)(b * p.KH + kvh) * p.KL) * E;
     const uint8_t* mp = p.kpad ? p.kpad + (size_t)b * p.KL : nullptr;
-    const int kend = p.causal ? (qi + 1 < p.KL ? qi + 1 : p.KL) : p.KL;
+    int kbeg, kend;
+    generic_key_range(p.causal, p.win_left, p.win_right, qi, p.KL, kbeg, kend);
     float m = -INFINITY, l = 0.f, oacc[kGenericMaxE / 64];
 #pragma unroll
     for (int j = 0; j < kGenericMaxE / 64; ++j) oacc[j] = 0.f;
-    for (int k0 = 0; k0 < kend; k0 += 64) {
+    for (int k0 = kbeg; k0 < kend; k0 += 64) {
         const int k = k0 + lane;
         const bool valid = k < kend && (!mp || mp[k] != 0);
         const int kc = k < p.KL ? k : p.KL - 1;
@@ -140,13 +149,14 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams 
     const T* kb = (const T*)p.k + ((size_t)(b * p.KH + kvh) * p.KL) * E;
     const T* vb = (const T*)p.v + ((size_t)(b * p.KH + kvh) * p.KL) * E;
     const uint8_t* mp = p.kpad ? p.kpad + (size_t)b * p.KL : nullptr;
-    const int kend = p.causal ? (qi + 1 < p.KL ? qi + 1 : p.KL) : p.KL;
+    int kbeg, kend;
+    generic_key_range(p.causal, p.win_left, p.win_right, qi, p.KL, kbeg, kend);
     const float lse = p.nl[row], delta = p.delta[row];
     const bool dead = !(lse > -INFINITY);                        // no visible key: zero gradients (deviation 3)
     float acc[kGenericMaxE / 64];
 #pragma unroll
     for (int j = 0; j < kGenericMaxE / 64; ++j) acc[j] = 0.f;
-    for (int k0 = 0; k0 < kend; k0 += 64) {
+    for (int k0 = kbeg; k0 < kend; k0 += 64) {
         const int k = k0 + lane;
         const bool valid = !dead && k < kend && (!mp || mp[k] != 0);
         const int kc = k < p.KL ? k : p.KL - 1;
@@ -201,12 +211,16 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParam
             const size_t rbase = ((size_t)b * p.QH + qh) * p.QL;
             const T* qb = (const T*)p.q + rbase * E;
             const T* dob = (const T*)p.d_o + rbase * E;
-            const int qbeg = p.causal ? (k / 64) * 64 : 0;        // queries < k see nothing of this key
-            for (int q0 = qbeg; q0 < p.QL; q0 += 64) {
+            // queries that see this key: q >= k (causal), q >= k - right, q <= k + left (window)
+            int qlo = p.causal ? k : 0;
+            if (p.win_right >= 0 && k - p.win_right > qlo) qlo = k - p.win_right;
+            const int qend = (p.win_left >= 0 && (long long)k + p.win_left + 1 < p.QL) ? k + p.win_left + 1 : p.QL;
+            const int qbeg = (qlo / 64) * 64;                      // queries < qlo see nothing of this key
+            for (int q0 = qbeg; q0 < qend; q0 += 64) {
                 const int q = q0 + lane;
                 const int qc = q < p.QL ? q : p.QL - 1;
                 const float lse = p.nl[rbase + qc];
-                const bool valid = q < p.QL && (!p.causal || k <= q) && lse > -INFINITY;
+                const bool valid = q < qend && q >= qlo && lse > -INFINITY;
                 float s = dot_lds(ks, qb + (size_t)qc * E, E) * p.scale;
                 if (p.pair) s += to_f32(((const T*)p.pair)[(((size_t)b * p.KL + k) * p.QL + qc) * p.QH + qh]);
                 const float pr = valid ? __expf(s - lse) : 0.f;

@@ -8,10 +8,25 @@
 
 namespace nnop {
 
+// Sliding window after normalisation (nnop_fa_opts, include/nnop_hip.h): -1 = unbounded side.  A side that removes no key is
+// unbounded here, so `on()` is false exactly when the call is the call without a window.
+struct FaWindow {
+    int left = -1, right = -1;
+    bool on() const { return left >= 0 || right >= 0; }
+};
+inline FaWindow fa_window(const nnop_fa_desc& d, const nnop_fa_opts* o) {
+    FaWindow w;
+    if (!o) return w;
+    w.left = o->window_left >= d.ql - 1 ? -1 : o->window_left;                          // j >= i - left holds for every j
+    w.right = (o->window_right >= d.kl - 1 || (d.causal && o->window_right >= 0)) ? -1 : o->window_right;   // implied by j <= i
+    return w;
+}
+
 struct FwdArgs {
     void *o, *ms, *ls;
     const void *q, *k, *v, *pair;
     const uint8_t* kpad;
+    FaWindow win = {};
 };
 
 struct BwdArgs {
@@ -20,6 +35,7 @@ struct BwdArgs {
     const uint8_t* kpad;
     void* workspace;
     size_t workspace_bytes;
+    FaWindow win = {};
 };
 
 // One per dtype (fa_fwd_{f32,f16,bf16}.hip).  Return an nnop_status.
@@ -27,9 +43,10 @@ template <typename T> int launch_fwd(const nnop_fa_desc& d, const FwdArgs& a, hi
 // Which kernel form launch_fwd picks (no launch): 0 = 32-row waves, 1 = split-KV, 2 = 64-row waves, 3 = the plain-HIP kernel of
 // fa_generic.hpp (embedding dims outside the tiled set), 4 = two waves per SIMD in alternating phases (fa_fwd_duo.hpp).
 enum FwdForm { kFormRow32 = 0, kFormSplit = 1, kFormW64 = 2, kFormGeneric = 3, kFormDuo = 4 };
-int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask);
+// A windowed problem (FaWindow::on) always runs kFormRow32 or kFormGeneric.
+int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed = false);
 // Which backward kernels launch_bwd picks (no launch): bit 0: dK/dV on fa_bwd_w64_kernel, bit 1: dQ on it (else fa_bwd.hpp's)
-int bwd_forms(const nnop_fa_desc& d, bool has_pair);
+int bwd_forms(const nnop_fa_desc& d, bool has_pair, bool windowed = false);
 // One per dtype (fa_bwd_{f32,f16,bf16}.hip).
 template <typename T> int launch_bwd(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s);
 

@@ -62,6 +62,14 @@ static inline size_t tensor_align(const nnop_fa_desc* d) {
     const bool tiled = emb_tiled(d->emb) || d->emb == 256;
     return tiled ? 16 : elem_bytes(d);
 }
+// per-call options (checked after check_desc, whose order is the reference's)
+static int check_opts(const nnop_fa_opts* o) {
+    if (!o) return NNOP_OK;
+    for (int i = 0; i < 6; ++i)
+        if (o->reserved[i] != 0) return NNOP_ERR_OPTS;
+    if (o->window_left < -1 || o->window_right < -1) return NNOP_ERR_OPTS;
+    return NNOP_OK;
+}
 // pair / dpair [B][KL][QL][QH]: inside one kv tile the kernels address the bias with 32-bit element offsets
 // (local key < 64) * QL * QH
 static int check_pair(const nnop_fa_desc* d) {
@@ -95,6 +103,19 @@ int nnop_debug_bwd_form(const nnop_fa_desc* d, int has_pair, int has_mask) {
     (void)has_mask;
     return bwd_forms(*d, has_pair != 0);
 }
+int nnop_debug_fwd_form_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, int has_pair, int has_mask) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
+    if (st != NNOP_OK) return st;
+    return fwd_form(*d, has_pair != 0, has_mask != 0, fa_window(*d, opts).on());
+}
+int nnop_debug_bwd_form_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, int has_pair, int has_mask) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
+    if (st != NNOP_OK) return st;
+    (void)has_mask;
+    return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on());
+}
 int nnop_debug_dev_build(void) {
 #ifdef NNOP_DEV_BUILD
     return 1;
@@ -119,6 +140,8 @@ const char* nnop_strerror(int status) {
         case NNOP_ERR_HIP: return "HIP runtime error at kernel launch.";
         case NNOP_ERR_ALIGN:
             return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls).";
+        case NNOP_ERR_OPTS:
+            return "Invalid attention options (a reserved field is not 0, or a window side is below -1).";
         default: return "unknown nnop status";
     }
 }
@@ -175,7 +198,13 @@ int nnop_shared_memory(int device, uint64_t* bytes) {
 
 int nnop_fa_fwd(const nnop_fa_desc* d, void* o, void* ms, void* ls, const void* q, const void* k,
                 const void* v, const void* pair, const uint8_t* kpad_mask, nnop_stream_t stream) {
-    const int st = check_desc(d);
+    return nnop_fa_fwd_ex(d, nullptr, o, ms, ls, q, k, v, pair, kpad_mask, stream);
+}
+
+int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* o, void* ms, void* ls, const void* q, const void* k,
+                   const void* v, const void* pair, const uint8_t* kpad_mask, nnop_stream_t stream) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
     if (st != NNOP_OK) return st;
     if (!o || !ms || !ls || !q || !k || !v) return NNOP_ERR_NULL;
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
@@ -185,7 +214,7 @@ int nnop_fa_fwd(const nnop_fa_desc* d, void* o, void* ms, void* ls, const void* 
             misaligned(ms, ea) || misaligned(ls, ea))
             return NNOP_ERR_ALIGN;
     }
-    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask};
+    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts)};
     hipStream_t s = (hipStream_t)stream;
     switch (d->dtype) {
         case NNOP_F32:  return launch_fwd<float>(*d, a, s);
@@ -288,7 +317,15 @@ int nnop_fa_bwd(const nnop_fa_desc* d, void* dq, void* dk, void* dv, void* dpair
                 const void* o, const void* ms, const void* ls, const void* q, const void* k,
                 const void* v, const void* pair, const uint8_t* kpad_mask, void* workspace,
                 size_t workspace_bytes, nnop_stream_t stream) {
-    const int st = check_desc(d);
+    return nnop_fa_bwd_ex(d, nullptr, dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes,
+                          stream);
+}
+
+int nnop_fa_bwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* dq, void* dk, void* dv, void* dpair, const void* d_o,
+                   const void* o, const void* ms, const void* ls, const void* q, const void* k, const void* v, const void* pair,
+                   const uint8_t* kpad_mask, void* workspace, size_t workspace_bytes, nnop_stream_t stream) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
     if (st != NNOP_OK) return st;
     if (!dq || !dk || !dv || !d_o || !o || !ms || !ls || !q || !k || !v || !workspace) return NNOP_ERR_NULL;
     if (pair && !dpair) return NNOP_ERR_NULL;
@@ -301,7 +338,7 @@ int nnop_fa_bwd(const nnop_fa_desc* d, void* dq, void* dk, void* dv, void* dpair
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(workspace, 16))
             return NNOP_ERR_ALIGN;
     }
-    BwdArgs a{dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes};
+    BwdArgs a{dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes, fa_window(*d, opts)};
     hipStream_t s = (hipStream_t)stream;
     switch (d->dtype) {
         case NNOP_F32:  return launch_bwd<float>(*d, a, s);

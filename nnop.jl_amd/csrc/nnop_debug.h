@@ -27,6 +27,12 @@ int nnop_debug_fwd_form(const struct nnop_fa_desc* d, int has_pair, int has_mask
  * otherwise the kernels of csrc/fa_bwd.hpp (or the plain-HIP ones for embedding dims outside the tiled set). */
 int nnop_debug_bwd_form(const struct nnop_fa_desc* d, int has_pair, int has_mask);
 
+/* The same two rules for a call with per-call options (nnop_fa_opts, include/nnop_hip.h; NULL = none): a window that does not
+ * normalise away always reports 0 / 3 forward and no w64 backward bits.  NNOP_ERR_OPTS for invalid options. */
+struct nnop_fa_opts;
+int nnop_debug_fwd_form_ex(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, int has_pair, int has_mask);
+int nnop_debug_bwd_form_ex(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, int has_pair, int has_mask);
+
 /* 1 when the library was built with `make DEV=1` (timing ablations, experimental kernel bodies compiled in). */
 int nnop_debug_dev_build(void);
 

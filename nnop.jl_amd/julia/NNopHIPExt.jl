@@ -32,6 +32,8 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
+export local_flash_attention
+
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
 
@@ -153,6 +155,88 @@ function NNop.∇flash_attention(
     causal::Bool, kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing,
 ) where T <: HipFloat
     return NNop.∇flash_attention(_to_roc(Δ, o)::ROCArray{T,4}, o, ms, ls, q, k, v, pair; causal, kpad_mask)
+end
+
+# ---- sliding-window (local) attention (include/nnop_hip.h: nnop_fa_opts, nnop_fa_fwd_ex / nnop_fa_bwd_ex, ABI version 7) --------------
+# NNop's own `flash_attention` keeps the reference's signature; the window is a function of this extension.  `window = (left, right)`
+# in flash-attn's `window_size` convention: query i sees key j iff i - left <= j <= i + right (1-based or 0-based alike: the rule
+# is on differences), -1 = unbounded side, on top of `causal` and `kpad_mask`; top-left aligned whatever QL and KL are.
+const ABI_VERSION = 7
+function check_abi()
+    v = ccall((:nnop_abi_version, libnnop()), Cint, ())
+    v == ABI_VERSION || error("libnnop_hip has ABI version $v, this extension needs $ABI_VERSION")
+    return nothing
+end
+
+# struct nnop_fa_opts
+struct FaOpts
+    window_left::Int32
+    window_right::Int32
+    reserved::NTuple{6, Int32}
+end
+FaOpts(window::Tuple{Integer, Integer}) = FaOpts(Int32(window[1]), Int32(window[2]), ntuple(_ -> Int32(0), 6))
+
+function local_flash_attention_fwd(
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, window::Tuple{Integer, Integer}, kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing,
+) where T <: HipFloat
+    check_abi()
+    d = Ref(desc(q, k, v, causal))
+    op = Ref(FaOpts(window))
+    o  = similar(q)
+    ms = ROCArray{T}(undef, size(q, 2), size(q, 3), size(q, 4))
+    ls = similar(ms)
+    st = GC.@preserve o ms ls q k v pair kpad_mask ccall((:nnop_fa_fwd_ex, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}),
+        d, op, devptr(o), devptr(ms), devptr(ls), devptr(q), devptr(k), devptr(v), devptr(pair), devptr(kpad_mask), hipstream())
+    check(st, q, k, v)
+    return o, ms, ls
+end
+
+function local_flash_attention_bwd(
+    Δ::ROCArray{T,4}, o::ROCArray{T,4}, ms::ROCArray{T,3}, ls::ROCArray{T,3},
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, window::Tuple{Integer, Integer}, kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing,
+) where T <: HipFloat
+    d = Ref(desc(q, k, v, causal))
+    op = Ref(FaOpts(window))
+    # a window needs no more scratch than the plain backward (with a pair bias it always takes the direct path)
+    nbytes = ccall((:nnop_fa_bwd_workspace_bytes, libnnop()), Csize_t, (Ptr{FaDesc},), d)
+    nbytes == 0 && error("libnnop_hip: invalid attention descriptor")
+    dq, dk, dv = similar(q), similar(k), similar(v)
+    dp = isnothing(pair) ? nothing : similar(pair)
+    ws = ROCArray{UInt8}(undef, nbytes)
+    st = GC.@preserve dq dk dv dp Δ o ms ls q k v pair kpad_mask ws ccall((:nnop_fa_bwd_ex, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        d, op, devptr(dq), devptr(dk), devptr(dv), devptr(dp), devptr(Δ), devptr(o), devptr(ms), devptr(ls),
+        devptr(q), devptr(k), devptr(v), devptr(pair), devptr(kpad_mask), devptr(ws), nbytes, hipstream())
+    check(st, q, k, v)
+    return dq, dk, dv, dp
+end
+
+"""
+    local_flash_attention(q, k, v, pair=nothing; causal, window, kpad_mask=nothing)
+
+Sliding-window (local) Flash Attention on the HIP kernels: `NNop.flash_attention` with query i seeing only keys
+i - window[1] .. i + window[2] (-1 = unbounded side).  Differentiable through the ChainRules rule below.
+"""
+local_flash_attention(q, k, v, pair = nothing; causal::Bool, window::Tuple{Integer, Integer}, kpad_mask = nothing) =
+    local_flash_attention_fwd(q, k, v, pair; causal, window, kpad_mask)[1]
+
+# the shape of the reference's rrule (src/attention_crc.jl:16-31): no tangent for the window or the mask
+function NNop.CRC.rrule(::typeof(local_flash_attention), q, k, v, pair = nothing;
+                                   causal::Bool, window::Tuple{Integer, Integer}, kpad_mask = nothing)
+    o, ms, ls = local_flash_attention_fwd(q, k, v, pair; causal, window, kpad_mask)
+    function local_flash_attention_pullback(Δ)
+        dq, dk, dv, dp = local_flash_attention_bwd(_to_roc(NNop.CRC.unthunk(Δ), o), o, ms, ls, q, k, v, pair;
+                                                   causal, window, kpad_mask)
+        return NNop.CRC.NoTangent(), dq, dk, dv, isnothing(pair) ? NNop.CRC.NoTangent() : dp
+    end
+    return o, local_flash_attention_pullback
 end
 
 # ---- several devices (include/nnop_hip.h: nnop_fa_shards, ABI version 6) -------------------------------------------------------------
