@@ -137,6 +137,34 @@ int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts,
                    nnop_stream_t stream);
 
 /*
+ * Learned per-head attention sinks (gpt-oss): nnop_fa_fwd_ex / nnop_fa_bwd_ex plus one trainable logit per QUERY head.
+ *   sinks : fp32 [QH], in the units of the scaled logits (scale * q.k).  Under GQA the query heads of one kv head each keep their own.
+ * The sink joins every row's softmax as one more column that has no value vector:
+ *   p_ij = exp(s_ij - m_i) / (sum_j' exp(s_ij' - m_i) + exp(sigma_h - m_i)),   o_i = sum_j p_ij v_j
+ * i.e. concatenate sigma_h to the row's logits, softmax, drop the sink's column (rows of p then need not sum to 1).  The causal rule,
+ * the window, kpad_mask and pair act on the real keys only (pair has no entry for the sink); the sink column is seen by every row.
+ *   ms = max(row max of the real logits, sigma_h), rounded to T as always;  ls = sum_j exp(s_ij - ms) + exp(sigma_h - ms), relative to the
+ *        rounded ms.  (o, ms, ls) stay self-consistent: the backward recomputes the right P from them.
+ *   A row that sees no key but a finite sink is NOT dead: o = 0, ms = sigma_h (rounded to T), ls = exp(sigma_h - ms) (1 up to that
+ *   rounding); in the backward its dq is 0 and it adds 0 to dsinks.
+ *   sigma_h = -inf is allowed and means "no sink" for that head: its results are the results without sinks.  +inf or NaN give NaN rows
+ *   (not checked).  A large sigma does not overflow (sigma = +200 with logits near 0: o ~ 0, ms = 200, ls ~ 1).
+ * Backward: dq, dk, dv, dpair as for nnop_fa_bwd_ex, and
+ *   dsinks : fp32 [QH], fully overwritten:  dsinks_h = -sum_{b,i} exp(sigma_h - ms_bhi) / ls_bhi * sum_e dO_bhie o_bhie,
+ *            computed from the T-valued ms, ls, o and dO that the call receives; bitwise the same whichever backward kernels run, and
+ *            run to run (fixed-order reduction, no atomics).
+ * sinks == NULL is exactly nnop_fa_fwd_ex / nnop_fa_bwd_ex (dsinks is then ignored, as dpair is without pair).  With sinks, a NULL
+ * dsinks is NNOP_ERR_NULL.  sinks and dsinks need 4-byte alignment (else NNOP_ERR_ALIGN).  Checks: the descriptor, the options, NULL
+ * pointers, alignment, in that order.  A sink needs no extra workspace: nnop_fa_bwd_workspace_bytes(_pair) are unchanged.
+ * Not supported by the sharding rectangles of nnop_fa_shards: a sharded dsinks would be a partial sum over batches.
+ */
+int nnop_fa_fwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks,
+                      void* o, void* ms, void* ls,
+                      const void* q, const void* k, const void* v,
+                      const void* pair, const uint8_t* kpad_mask,
+                      nnop_stream_t stream);
+
+/*
  * Scratch the backward needs (replaces the reference's internal Δ_scaled / δ temporaries,
  * src/attention_bwd.jl:224-225).  Returns 0 for an invalid descriptor.
  */
@@ -175,6 +203,14 @@ int nnop_fa_bwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts,
                    const void* pair, const uint8_t* kpad_mask,
                    void* workspace, size_t workspace_bytes,
                    nnop_stream_t stream);
+/* The same with learned attention sinks (nnop_fa_fwd_sinks above; sinks == NULL: exactly nnop_fa_bwd_ex, dsinks ignored). */
+int nnop_fa_bwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float* dsinks,
+                      void* dq, void* dk, void* dv, void* dpair,
+                      const void* d_o, const void* o, const void* ms, const void* ls,
+                      const void* q, const void* k, const void* v,
+                      const void* pair, const uint8_t* kpad_mask,
+                      void* workspace, size_t workspace_bytes,
+                      nnop_stream_t stream);
 
 /*
  * Llama rotary embedding: contract of NNop._llama_rope(q, k, cos, sin; bwd)

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = (
     "nnop_fa_bwd",
     "nnop_fa_fwd_ex",
     "nnop_fa_bwd_ex",
+    "nnop_fa_fwd_sinks",
+    "nnop_fa_bwd_sinks",
     "nnop_llama_rope",
     "nnop_online_softmax",
     "nnop_online_softmax_bwd",
@@ -148,6 +150,11 @@ def load():
     lib.nnop_fa_bwd_ex.restype = C.c_int
     lib.nnop_fa_bwd_ex.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                    u8p, vp, C.c_size_t, vp]
+    lib.nnop_fa_fwd_sinks.restype = C.c_int
+    lib.nnop_fa_fwd_sinks.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
+    lib.nnop_fa_bwd_sinks.restype = C.c_int
+    lib.nnop_fa_bwd_sinks.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      u8p, vp, C.c_size_t, vp]
     lib.nnop_llama_rope.restype = C.c_int
     lib.nnop_llama_rope.argtypes = [C.POINTER(RopeDesc), vp, vp, vp, vp, vp, vp, C.c_float, vp]
     lib.nnop_online_softmax.restype = C.c_int

@@ -142,48 +142,73 @@ def bwd_workspace_bytes(q, k, v, *, causal: bool, pair: bool = False) -> int:
     return int(f(C.byref(_desc(q, k, v, causal))))
 
 
-def _fwd_call(lib, opts, d, *args):
-    """nnop_fa_fwd, or nnop_fa_fwd_ex when there are per-call options (window=None issues exactly the old call)"""
+def _fwd_call(lib, opts, d, *args, sinks=None):
+    """nnop_fa_fwd, or nnop_fa_fwd_ex when there are per-call options (window=None issues exactly the old call), or
+    nnop_fa_fwd_sinks with sinks (a fp32 tensor; sinks=None issues exactly the call without them)"""
+    if sinks is not None:
+        return lib.nnop_fa_fwd_sinks(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks), *args)
     if opts is None:
         return lib.nnop_fa_fwd(C.byref(d), *args)
     return lib.nnop_fa_fwd_ex(C.byref(d), C.byref(opts), *args)
 
 
-def _bwd_call(lib, opts, d, *args):
+def _bwd_call(lib, opts, d, *args, sinks=None, dsinks=None):
+    if sinks is not None:
+        return lib.nnop_fa_bwd_sinks(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks), _ptr(dsinks),
+                                     *args)
     if opts is None:
         return lib.nnop_fa_bwd(C.byref(d), *args)
     return lib.nnop_fa_bwd_ex(C.byref(d), C.byref(opts), *args)
 
 
-def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
+def _sinks_f32(sinks, q):
+    """Learned attention sinks as the library takes them: a contiguous fp32 [QH] tensor on q's device (None stays None)."""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, torch.Tensor) or sinks.dim() != 1 or sinks.shape[0] != q.shape[1]:
+        raise TypeError(f"sinks must be a 1-D tensor [QH] = [{q.shape[1]}], got "
+                        f"{tuple(sinks.shape) if isinstance(sinks, torch.Tensor) else type(sinks).__name__}")
+    if sinks.dtype not in _DTYPES:
+        raise TypeError(f"sinks must be float32, float16 or bfloat16, got {sinks.dtype}")
+    if sinks.device != q.device:
+        raise TypeError("sinks must live on q's device")
+    return sinks.detach().to(torch.float32).contiguous()
+
+
+def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
     """Raw ``nnop_fa_fwd`` into caller-owned, preallocated outputs (the C ABI's ownership model:
     the caller allocates everything).  No checks beyond the library's own; contiguous tensors only.
-    Used by bench.py so that a timed step is exactly one library call.  ``window``: see flash_attention."""
+    Used by bench.py so that a timed step is exactly one library call.  ``window``, ``sinks``: see flash_attention
+    (``sinks`` here: a contiguous fp32 [QH] tensor, passed as it is)."""
     d = _desc(q, k, v, causal)
     st = _fwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                   _ptr(pair), _ptr(kpad_mask), _stream(q))
+                   _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
-def fa_bwd_into(dq, dk, dv, dpair, ws, dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
-    """Raw ``nnop_fa_bwd`` into caller-owned outputs and workspace (see fa_fwd_into)."""
+def fa_bwd_into(dq, dk, dv, dpair, ws, dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None,
+                sinks=None, dsinks=None):
+    """Raw ``nnop_fa_bwd`` into caller-owned outputs and workspace (see fa_fwd_into).  With ``sinks``, ``dsinks`` is a
+    caller-owned fp32 [QH] tensor that receives their gradient."""
     d = _desc(q, k, v, causal)
     st = _bwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
                    _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                   _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q))
+                   _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q), sinks=sinks, dsinks=dsinks)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
-def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
+def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
     """``NNop._flash_attention`` (src/attention.jl:133-177): returns ``(o, ms, ls)``.
 
-    Asynchronous on the current torch stream, like the reference's KA launch.  ``window``: see flash_attention.
+    Asynchronous on the current torch stream, like the reference's KA launch.  ``window``, ``sinks``: see flash_attention
+    (with sinks, ``ms`` and ``ls`` include the sink column).
     """
     lib = _lib.load()
     opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
+    sinks = _sinks_f32(sinks, q)
     if k.shape[0] != q.shape[0]:
         raise NNopError(f"Batch of K `{k.shape[0]}` must be the same as of Q `{q.shape[0]}`.")
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
@@ -197,18 +222,19 @@ def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window
         ms = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :167
         ls = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :168
         st = _fwd_call(lib, opts, d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                       _ptr(pair), _ptr(kpad_mask), _stream(q))
+                       _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
     return o, ms, ls
 
 
-def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
-    """``NNop.∇flash_attention`` (src/attention_bwd.jl:199-275): returns ``(dq, dk, dv, dpair|None)``.
-    ``window``: the forward's (see flash_attention)."""
+def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
+    """``NNop.∇flash_attention`` (src/attention_bwd.jl:199-275): returns ``(dq, dk, dv, dpair|None)``, and with ``sinks``
+    ``(dq, dk, dv, dpair|None, dsinks)`` (dsinks: fp32 [QH]).  ``window``, ``sinks``: the forward's (see flash_attention)."""
     lib = _lib.load()
     opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
+    sinks = _sinks_f32(sinks, q)
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     dO, o, ms, ls = dO.contiguous(), o.contiguous(), ms.contiguous(), ls.contiguous()
     if dO.dtype != q.dtype or dO.shape != q.shape:
@@ -233,6 +259,7 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
         dk = torch.empty_like(k)
         dv = torch.empty_like(v)
         dpair = torch.empty_like(pair) if pair is not None else None
+        dsinks = torch.empty_like(sinks) if sinks is not None else None
         nbytes = small = int(lib.nnop_fa_bwd_workspace_bytes(C.byref(d)))
         if nbytes != 0 and pair is not None and opts is None:
             # staged pair-bias path: two head-major bias-sized scratch matrices on top (the library returns the small size
@@ -250,9 +277,11 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
         st = _bwd_call(lib, opts, d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
                        _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                       _ptr(ws), C.c_size_t(nbytes), _stream(q))
+                       _ptr(ws), C.c_size_t(nbytes), _stream(q), sinks=sinks, dsinks=dsinks)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
+    if sinks is not None:
+        return dq, dk, dv, dpair, dsinks
     return dq, dk, dv, dpair
 
 
@@ -262,33 +291,43 @@ class _FlashAttentionFn(torch.autograd.Function):
     no tangent for kpad_mask."""
 
     @staticmethod
-    def forward(ctx, q, k, v, pair, kpad_mask, causal, window=None):
-        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window)
+    def forward(ctx, q, k, v, pair, kpad_mask, causal, window=None, sinks=None):
+        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks)
         ctx.save_for_backward(o, ms, ls, q, k, v, pair if pair is not None else torch.empty(0),
-                              kpad_mask if kpad_mask is not None else torch.empty(0))
+                              kpad_mask if kpad_mask is not None else torch.empty(0),
+                              sinks if sinks is not None else torch.empty(0))
         ctx.has_pair, ctx.has_mask, ctx.causal, ctx.window = pair is not None, kpad_mask is not None, bool(causal), window
+        ctx.has_sinks = sinks is not None
         return o
 
     @staticmethod
     def backward(ctx, dO):
-        o, ms, ls, q, k, v, pair, mask = ctx.saved_tensors
-        dq, dk, dv, dpair = grad_flash_attention(
+        o, ms, ls, q, k, v, pair, mask, sinks = ctx.saved_tensors
+        grads = grad_flash_attention(
             dO, o, ms, ls, q, k, v, pair if ctx.has_pair else None,
-            causal=ctx.causal, kpad_mask=mask if ctx.has_mask else None, window=ctx.window)
-        return dq, dk, dv, dpair, None, None, None
+            causal=ctx.causal, kpad_mask=mask if ctx.has_mask else None, window=ctx.window,
+            sinks=sinks if ctx.has_sinks else None)
+        dq, dk, dv, dpair = grads[:4]
+        dsinks = grads[4].to(sinks.dtype) if ctx.has_sinks else None     # in the sinks tensor's dtype
+        return dq, dk, dv, dpair, None, None, None, dsinks
 
 
-def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None):
+def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
     """``NNop.flash_attention(q, k, v, pair=nothing; causal, kpad_mask=nothing)``
     (src/attention_crc.jl:4-14).  ``causal`` is a required keyword, as in the reference.
     Returns ``o``; differentiable w.r.t. q, k, v, pair through the rrule above.
 
     ``window=(left, right)``: sliding-window (local) attention in flash-attn's ``window_size`` convention -- query i
     sees key j only if ``i - left <= j <= i + right`` (on top of ``causal`` and ``kpad_mask``); ``-1`` leaves a side
-    unbounded.  Top-left aligned (query i lines up with key i) whatever QL and KL are.  ``None``: no window."""
+    unbounded.  Top-left aligned (query i lines up with key i) whatever QL and KL are.  ``None``: no window.
+
+    ``sinks``: learned per-head attention sinks (gpt-oss), a 1-D ``[QH]`` float tensor on q's device, one logit per
+    query head in the units of the scaled logits.  Each row's softmax gets one more column of logit ``sinks[h]`` and no
+    value vector (concatenate, softmax, drop that column); causal, window, kpad_mask and pair act on the real keys only.
+    ``-inf`` means no sink for that head.  Differentiable: ``sinks.requires_grad`` gets a gradient in its own dtype."""
     if window is not None:
         window = tuple(window)
     if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (q, k, v, pair)):
-        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal), window)
-    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window)[0]
+            t is not None and t.requires_grad for t in (q, k, v, pair, sinks)):
+        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal), window, sinks)
+    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks)[0]

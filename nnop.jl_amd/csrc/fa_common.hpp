@@ -96,6 +96,20 @@ NNOP_DEV float half_swap_sum(float x) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// Learned attention sink (nnop_fa_fwd_sinks): one more partial (m = s2, l = 1, O = 0) merged into a row's finished (m, l, O) in the
+// forward epilogues.  s2 = sigma * log2(e), the units of the exponent reference m (log2 units of the scaled logits); mt is the row max
+// in the same units.  The new reference is max(m, s2), never an old one plus exp2(s2 - m), so a large sigma cannot overflow.  Returns
+// the factor O must be scaled by.  s2 = -inf: no sink, nothing changes (a row without a visible key keeps l = 0 and its NaN).
+NNOP_DEV float sink_merge(float s2, float& m, float& l, float& mt) {
+    if (s2 == -INFINITY) return 1.f;
+    const float mm = fmaxf(m, s2);
+    const float a = m == -INFINITY ? 0.f : fast_exp2(m - mm);
+    l = l * a + fast_exp2(s2 - mm);
+    m = mm;
+    mt = fmaxf(mt, s2);
+    return a;
+}
+
 // Force a register-resident value to have LANDED here: the compiler must insert the s_waitcnt for
 // the load that produces it at this point, not at its first use.  Used before a pipelined loop for
 // loads issued ahead of it: vmcnt retires in order, so a wait left inside the loop for an OLD load

@@ -33,12 +33,14 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     constexpr int BK = (E >= 256 || (E >= 128 && (MODE == 2 || sizeof(T) == 4))) ? 32 : 64;
     constexpr int lds = fa_fwd_lds_bytes<T, E, BK>();
     static_assert(lds <= 160 * 1024, "LDS budget (160 KiB per CU on gfx950)");
-    auto kern = fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
-    static unsigned long long lds_done = 0;
-    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
+    // learned sinks: the SINK = true instantiation (the code of the calls without them stays as it is)
+    auto kern = a.sinks ? fa_fwd_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
+    static unsigned long long lds_done[2] = {0, 0};
+    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     p.o = a.o; p.ms = a.ms; p.ls = a.ls;
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    p.sinks = a.sinks;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
     constexpr int rows = 32 * QB * NW;
@@ -76,13 +78,14 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
 template <typename T, int E>
 static int launch_fwd_split(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     constexpr int lds = fa_fwd_split_lds_bytes<T, E>();
-    void (*kern)(const FwdParams) = fa_fwd_split_kernel<T, E>;
+    void (*kern)(const FwdParams) = a.sinks ? fa_fwd_split_sink_kernel<T, E> : fa_fwd_split_kernel<T, E>;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static unsigned long long lds_done = 0;
-    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
+    static unsigned long long lds_done[2] = {0, 0};
+    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     p.o = a.o; p.ms = a.ms; p.ls = a.ls;
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = nullptr;
+    p.sinks = a.sinks;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = 0;
     p.n_qblk = (d.ql + 255) / 256;
@@ -131,12 +134,13 @@ static int launch_fwd_w64(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     constexpr int EV = E == 256 ? 128 : E;                   // E = 256: two 128-column halves of O per block (fa_fwd_w64.hpp)
     constexpr int lds = fa_fwd_w64_lds_bytes<T, E, EV>(MODE != 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fa_fwd_w64_kernel<T, E, MODE, PRE, EV>;
-    static unsigned long long lds_done = 0;
-    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
+    auto kern = a.sinks ? fa_fwd_w64_sink_kernel<T, E, MODE, PRE, EV> : fa_fwd_w64_kernel<T, E, MODE, PRE, EV>;
+    static unsigned long long lds_done[2] = {0, 0};
+    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     p.o = a.o; p.ms = a.ms; p.ls = a.ls;
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = a.kpad;
+    p.sinks = a.sinks;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
     p.n_qblk = (d.ql + 255) / 256;
@@ -157,12 +161,13 @@ template <typename T, int E, int MODE, int NZ>
 static int launch_fwd_duo(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     constexpr int lds = fa_fwd_duo_lds_bytes<T, E>(MODE != 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fa_fwd_duo_kernel<T, E, MODE, NZ>;
-    static unsigned long long lds_done = 0;
-    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
+    auto kern = a.sinks ? fa_fwd_duo_sink_kernel<T, E, MODE, NZ> : fa_fwd_duo_kernel<T, E, MODE, NZ>;
+    static unsigned long long lds_done[2] = {0, 0};
+    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     p.o = a.o; p.ms = a.ms; p.ls = a.ls;
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = a.kpad;
+    p.sinks = a.sinks;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
     p.n_qblk = (d.ql + 128 * NZ - 1) / (128 * NZ);
@@ -353,6 +358,7 @@ template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const
     FwdParams p;
     p.o = a.o; p.ms = a.ms; p.ls = a.ls;
     p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    p.sinks = a.sinks;
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
     p.win_left = a.win.left; p.win_right = a.win.right;
@@ -361,7 +367,8 @@ template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const
     const long long n_rows = (long long)d.batch * d.qh * d.ql;
     const long long grid = (n_rows + 3) / 4;
     if (grid > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    hipLaunchKernelGGL((fa_fwd_generic_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
+    if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
+    else hipLaunchKernelGGL((fa_fwd_generic_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 

@@ -33,8 +33,8 @@ template <typename T, int E> constexpr int fa_fwd_split_lds_bytes() {
     return rings > handoff ? rings : handoff;
 }
 
-template <typename T, int E>
-__global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) {
+template <typename T, int E, bool SINK>                  // SINK: learned attention sinks (fa_fwd.hpp)
+__device__ __forceinline__ void fa_fwd_split_body(const FwdParams p) {
     static_assert(sizeof(T) == 2, "16-bit element types only");
     using frag_t = typename Elem<T>::frag;
     using KImg   = RowImg<T, E>;
@@ -215,15 +215,20 @@ __global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) {
     __syncthreads();
     if (grp == 0) {
         const float m2b = xch[(EB * 16 + 0) * 64], mtb = xch[(EB * 16 + 1) * 64], lb = xch[(EB * 16 + 2) * 64];
-        const float mn = fmaxf(m2, m2b);
-        const float fa = (m2 == -INFINITY) ? 0.f : fast_exp2(m2 - mn);
-        const float fb = (m2b == -INFINITY) ? 0.f : fast_exp2(m2b - mn);
-        const float mtt = fmaxf(mt, mtb);
+        float mn = fmaxf(m2, m2b);
+        float fa = (m2 == -INFINITY) ? 0.f : fast_exp2(m2 - mn);
+        float fb = (m2b == -INFINITY) ? 0.f : fast_exp2(m2b - mn);
+        float mtt = fmaxf(mt, mtb);
 #if NNOP_SPLIT_MFMASUM
-        const float ltot = lsum * fa + lb * fb;            // the MFMA sums already span both lane halves' keys
+        float ltot = lsum * fa + lb * fb;                  // the MFMA sums already span both lane halves' keys
 #else
-        const float ltot = half_swap_sum(lsum * fa + lb * fb);
+        float ltot = half_swap_sum(lsum * fa + lb * fb);
 #endif
+        if constexpr (SINK) {                              // the sink: one more partial of the merge (wave-uniform)
+            const float g = sink_merge(p.sinks[qh] * kLog2e, mn, ltot, mtt);
+            fa *= g;
+            fb *= g;
+        }
         const float inv = 1.0f / ltot;
         if (qi < p.QL) {
             T* orow = (T*)p.o + ((size_t)bh * p.QL + qi) * E;
@@ -255,5 +260,10 @@ __global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) {
         }
     }
 }
+
+template <typename T, int E>
+__global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) { fa_fwd_split_body<T, E, false>(p); }
+template <typename T, int E>
+__global__ __launch_bounds__(1024) void fa_fwd_split_sink_kernel(const FwdParams p) { fa_fwd_split_body<T, E, true>(p); }
 
 }  // namespace nnop

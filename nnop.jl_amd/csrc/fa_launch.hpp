@@ -27,6 +27,7 @@ struct FwdArgs {
     const void *q, *k, *v, *pair;
     const uint8_t* kpad;
     FaWindow win = {};
+    const float* sinks = nullptr;       // learned per-head attention sinks, fp32 [QH] (nnop_fa_fwd_sinks); nullptr = none
 };
 
 struct BwdArgs {
@@ -36,6 +37,8 @@ struct BwdArgs {
     void* workspace;
     size_t workspace_bytes;
     FaWindow win = {};
+    const float* sinks = nullptr;       // nnop_fa_bwd_sinks: the forward's sinks, and their gradient fp32 [QH] (launch_bwd_sinks)
+    float* dsinks = nullptr;
 };
 
 // One per dtype (fa_fwd_{f32,f16,bf16}.hip).  Return an nnop_status.
@@ -49,6 +52,8 @@ int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed 
 int bwd_forms(const nnop_fa_desc& d, bool has_pair, bool windowed = false);
 // One per dtype (fa_bwd_{f32,f16,bf16}.hip).
 template <typename T> int launch_bwd(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s);
+// dsinks from dO, o, ms, ls alone, whichever backward kernels ran (fa_sinks.hpp); uses the workspace, after launch_bwd on the same stream.
+template <typename T> int launch_bwd_sinks(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s);
 
 // rope.hip
 int launch_rope(const nnop_rope_desc& d, void* qo, void* ko, const void* q, const void* k, const void* cos,

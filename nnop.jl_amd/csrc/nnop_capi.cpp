@@ -203,6 +203,12 @@ int nnop_fa_fwd(const nnop_fa_desc* d, void* o, void* ms, void* ls, const void* 
 
 int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* o, void* ms, void* ls, const void* q, const void* k,
                    const void* v, const void* pair, const uint8_t* kpad_mask, nnop_stream_t stream) {
+    return nnop_fa_fwd_sinks(d, opts, nullptr, o, ms, ls, q, k, v, pair, kpad_mask, stream);
+}
+
+int nnop_fa_fwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, void* o, void* ms, void* ls,
+                      const void* q, const void* k, const void* v, const void* pair, const uint8_t* kpad_mask,
+                      nnop_stream_t stream) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
     if (st != NNOP_OK) return st;
@@ -211,10 +217,10 @@ int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* o, voi
     {
         const size_t ta = tensor_align(d), ea = elem_bytes(d);
         if (misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
-            misaligned(ms, ea) || misaligned(ls, ea))
+            misaligned(ms, ea) || misaligned(ls, ea) || misaligned(sinks, sizeof(float)))
             return NNOP_ERR_ALIGN;
     }
-    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts)};
+    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts), sinks};
     hipStream_t s = (hipStream_t)stream;
     switch (d->dtype) {
         case NNOP_F32:  return launch_fwd<float>(*d, a, s);
@@ -324,26 +330,45 @@ int nnop_fa_bwd(const nnop_fa_desc* d, void* dq, void* dk, void* dv, void* dpair
 int nnop_fa_bwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* dq, void* dk, void* dv, void* dpair, const void* d_o,
                    const void* o, const void* ms, const void* ls, const void* q, const void* k, const void* v, const void* pair,
                    const uint8_t* kpad_mask, void* workspace, size_t workspace_bytes, nnop_stream_t stream) {
+    return nnop_fa_bwd_sinks(d, opts, nullptr, nullptr, dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace,
+                             workspace_bytes, stream);
+}
+
+int nnop_fa_bwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float* dsinks, void* dq, void* dk,
+                      void* dv, void* dpair, const void* d_o, const void* o, const void* ms, const void* ls, const void* q,
+                      const void* k, const void* v, const void* pair, const uint8_t* kpad_mask, void* workspace,
+                      size_t workspace_bytes, nnop_stream_t stream) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
     if (st != NNOP_OK) return st;
+    if (!sinks) dsinks = nullptr;                          // ignored without sinks, as dpair is without pair
     if (!dq || !dk || !dv || !d_o || !o || !ms || !ls || !q || !k || !v || !workspace) return NNOP_ERR_NULL;
     if (pair && !dpair) return NNOP_ERR_NULL;
+    if (sinks && !dsinks) return NNOP_ERR_NULL;
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
     if (workspace_bytes < bwd_workspace_bytes(*d)) return NNOP_ERR_WORKSPACE;
     {
         const size_t ta = tensor_align(d), ea = elem_bytes(d);
         if (misaligned(dq, ta) || misaligned(dk, ta) || misaligned(dv, ta) || misaligned(dpair, ta) || misaligned(d_o, ta) ||
             misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
-            misaligned(ms, ea) || misaligned(ls, ea) || misaligned(workspace, 16))
+            misaligned(ms, ea) || misaligned(ls, ea) || misaligned(workspace, 16) || misaligned(sinks, sizeof(float)) ||
+            misaligned(dsinks, sizeof(float)))
             return NNOP_ERR_ALIGN;
     }
-    BwdArgs a{dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes, fa_window(*d, opts)};
+    BwdArgs a{dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes, fa_window(*d, opts),
+              sinks, dsinks};
     hipStream_t s = (hipStream_t)stream;
+    // dQ, dK, dV (and dpair) need nothing for a sink: they recompute P from (ms, ls), which include it.  dsinks: one more pass behind them
     switch (d->dtype) {
-        case NNOP_F32:  return launch_bwd<float>(*d, a, s);
-        case NNOP_F16:  return launch_bwd<_Float16>(*d, a, s);
-        case NNOP_BF16: return launch_bwd<__bf16>(*d, a, s);
+        case NNOP_F32:
+            st = launch_bwd<float>(*d, a, s);
+            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<float>(*d, a, s) : st;
+        case NNOP_F16:
+            st = launch_bwd<_Float16>(*d, a, s);
+            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<_Float16>(*d, a, s) : st;
+        case NNOP_BF16:
+            st = launch_bwd<__bf16>(*d, a, s);
+            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<__bf16>(*d, a, s) : st;
     }
     return NNOP_ERR_DTYPE;
 }

@@ -32,7 +32,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention
+export local_flash_attention, flash_attention_sinks
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -237,6 +237,78 @@ function NNop.CRC.rrule(::typeof(local_flash_attention), q, k, v, pair = nothing
         return NNop.CRC.NoTangent(), dq, dk, dv, isnothing(pair) ? NNop.CRC.NoTangent() : dp
     end
     return o, local_flash_attention_pullback
+end
+
+# ---- learned attention sinks (include/nnop_hip.h: nnop_fa_fwd_sinks / nnop_fa_bwd_sinks) ---------------------------------------------
+# One trainable logit per QUERY head (gpt-oss): every row's softmax gets one more column of logit sinks[h] and no value vector.  `causal`,
+# `window` and `kpad_mask` act on the real keys only; -Inf32 = no sink for that head.  (o, ms, ls) include the sink, so the backward
+# kernels recompute the right P; the library adds the gradient of the sinks.  Not part of the sharding helpers below.
+function flash_attention_sinks_fwd(
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, sinks::ROCVector{Float32}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, window::Tuple{Integer, Integer} = (-1, -1), kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing,
+) where T <: HipFloat
+    check_abi()
+    length(sinks) == size(q, 3) || error("sinks must have one entry per query head ($(size(q, 3))), got $(length(sinks))")
+    d = Ref(desc(q, k, v, causal))
+    op = Ref(FaOpts(window))
+    o  = similar(q)
+    ms = ROCArray{T}(undef, size(q, 2), size(q, 3), size(q, 4))
+    ls = similar(ms)
+    st = GC.@preserve o ms ls q k v sinks pair kpad_mask ccall((:nnop_fa_fwd_sinks, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}, Ptr{Cvoid}),
+        d, op, devptr(sinks), devptr(o), devptr(ms), devptr(ls), devptr(q), devptr(k), devptr(v), devptr(pair), devptr(kpad_mask),
+        hipstream())
+    check(st, q, k, v)
+    return o, ms, ls
+end
+
+function flash_attention_sinks_bwd(
+    Δ::ROCArray{T,4}, o::ROCArray{T,4}, ms::ROCArray{T,3}, ls::ROCArray{T,3},
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, sinks::ROCVector{Float32}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, window::Tuple{Integer, Integer} = (-1, -1), kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing,
+) where T <: HipFloat
+    d = Ref(desc(q, k, v, causal))
+    op = Ref(FaOpts(window))
+    # a sink needs no more scratch than the plain backward
+    nbytes = ccall((:nnop_fa_bwd_workspace_bytes, libnnop()), Csize_t, (Ptr{FaDesc},), d)
+    nbytes == 0 && error("libnnop_hip: invalid attention descriptor")
+    dq, dk, dv = similar(q), similar(k), similar(v)
+    dp = isnothing(pair) ? nothing : similar(pair)
+    ds = similar(sinks)                                        # fully overwritten by the library
+    ws = ROCArray{UInt8}(undef, nbytes)
+    st = GC.@preserve dq dk dv dp ds Δ o ms ls q k v sinks pair kpad_mask ws ccall((:nnop_fa_bwd_sinks, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Ptr{Cvoid},                    # sinks dsinks
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},                      # dq dk dv dpair
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},                      # Δ o ms ls
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},          # q k v pair kpad_mask
+         Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),                                    # workspace, bytes, stream
+        d, op, devptr(sinks), devptr(ds), devptr(dq), devptr(dk), devptr(dv), devptr(dp), devptr(Δ), devptr(o), devptr(ms),
+        devptr(ls), devptr(q), devptr(k), devptr(v), devptr(pair), devptr(kpad_mask), devptr(ws), nbytes, hipstream())
+    check(st, q, k, v)
+    return dq, dk, dv, dp, ds
+end
+
+"""
+    flash_attention_sinks(q, k, v, sinks, pair=nothing; causal, window=(-1, -1), kpad_mask=nothing)
+
+Flash Attention with learned per-head attention sinks on the HIP kernels (gpt-oss): `sinks::ROCVector{Float32}` holds one logit per
+query head in the units of the scaled logits; each row's softmax gets that extra column, whose share of the row is dropped.  `window`
+as for `local_flash_attention`.  Differentiable w.r.t. q, k, v, sinks (and pair) through the ChainRules rule below.
+"""
+flash_attention_sinks(q, k, v, sinks, pair = nothing; causal::Bool, window::Tuple{Integer, Integer} = (-1, -1), kpad_mask = nothing) =
+    flash_attention_sinks_fwd(q, k, v, sinks, pair; causal, window, kpad_mask)[1]
+
+# the shape of local_flash_attention's rule, plus a tangent for the sinks
+function NNop.CRC.rrule(::typeof(flash_attention_sinks), q, k, v, sinks, pair = nothing;
+                                   causal::Bool, window::Tuple{Integer, Integer} = (-1, -1), kpad_mask = nothing)
+    o, ms, ls = flash_attention_sinks_fwd(q, k, v, sinks, pair; causal, window, kpad_mask)
+    function flash_attention_sinks_pullback(Δ)
+        dq, dk, dv, dp, ds = flash_attention_sinks_bwd(_to_roc(NNop.CRC.unthunk(Δ), o), o, ms, ls, q, k, v, sinks, pair;
+                                                       causal, window, kpad_mask)
+        return NNop.CRC.NoTangent(), dq, dk, dv, ds, isnothing(pair) ? NNop.CRC.NoTangent() : dp
+    end
+    return o, flash_attention_sinks_pullback
 end
 
 # ---- several devices (include/nnop_hip.h: nnop_fa_shards, ABI version 6) -------------------------------------------------------------
