@@ -165,6 +165,32 @@ int nnop_fa_fwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const flo
                       nnop_stream_t stream);
 
 /*
+ * Logit soft-capping (Gemma-2: c = 50, Grok-1: c = 30; flash-attn's `softcap`): nnop_fa_fwd_sinks / nnop_fa_bwd_sinks plus a cap c > 0
+ * on the SCALED scores.  With scale = 1/sqrt(E):
+ *     s_ij = scale * q_i.k_j
+ *     z_ij = c * tanh(s_ij / c)                  the capped score
+ *     x_ij = z_ij + pair_ij                      pair is added AFTER the cap and is never capped
+ *     x_ij = -inf where the causal rule, the window or kpad_mask hide key j from query i
+ *     P    = softmax_j(x_ij [, sinks_h as one more column, not capped]),   o = P v
+ *     ms, ls: row max and sum-exp of x (with the sink where given), as always
+ * Backward, with dS = P o (dP - delta), the gradient with respect to x, as always:
+ *     dpair = dS                                 unchanged
+ *     dS'   = dS o (1 - (z / c)^2)               through the tanh
+ *     dQ = scale dS' K     dK = scale dS'^T Q (summed over the GQA group)     dV = P^T dO (unchanged)     dsinks: unchanged
+ * Rows that see no key keep their convention (NaN in o, ms = -inf, dq = 0).  The cap arithmetic is fp32 for every element type.
+ * softcap == 0 means no cap: the call is exactly nnop_fa_fwd_sinks / nnop_fa_bwd_sinks (the same kernels, bitwise the same results).
+ * A negative, NaN or infinite softcap is NNOP_ERR_OPTS.  Checks: the descriptor, the options, the cap, NULL pointers, alignment, in
+ * that order.  The forward and the backward of one problem take the same cap.  A cap needs no extra workspace
+ * (nnop_fa_bwd_workspace_bytes(_pair) are unchanged); with a cap and a pair bias the backward always takes the direct path, whatever
+ * `workspace_bytes` is (as with a window).
+ */
+int nnop_fa_fwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float softcap,
+                        void* o, void* ms, void* ls,
+                        const void* q, const void* k, const void* v,
+                        const void* pair, const uint8_t* kpad_mask,
+                        nnop_stream_t stream);
+
+/*
  * Scratch the backward needs (replaces the reference's internal Δ_scaled / δ temporaries,
  * src/attention_bwd.jl:224-225).  Returns 0 for an invalid descriptor.
  */
@@ -211,6 +237,15 @@ int nnop_fa_bwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const flo
                       const void* pair, const uint8_t* kpad_mask,
                       void* workspace, size_t workspace_bytes,
                       nnop_stream_t stream);
+
+/* The same with logit soft-capping (nnop_fa_fwd_softcap above; softcap == 0: exactly nnop_fa_bwd_sinks). */
+int nnop_fa_bwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float* dsinks, float softcap,
+                        void* dq, void* dk, void* dv, void* dpair,
+                        const void* d_o, const void* o, const void* ms, const void* ls,
+                        const void* q, const void* k, const void* v,
+                        const void* pair, const uint8_t* kpad_mask,
+                        void* workspace, size_t workspace_bytes,
+                        nnop_stream_t stream);
 
 /*
  * Llama rotary embedding: contract of NNop._llama_rope(q, k, cos, sin; bwd)

@@ -7,6 +7,7 @@ absent the import of the product path raises.
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +44,8 @@ EXPORTED_SYMBOLS = (
     "nnop_fa_bwd_ex",
     "nnop_fa_fwd_sinks",
     "nnop_fa_bwd_sinks",
+    "nnop_fa_fwd_softcap",
+    "nnop_fa_bwd_softcap",
     "nnop_llama_rope",
     "nnop_online_softmax",
     "nnop_online_softmax_bwd",
@@ -60,8 +63,9 @@ EXPORTED_SYMBOLS = (
 
 # Test-only hooks (csrc/nnop_debug.h): exported by the library, deliberately NOT in the public header.
 DEBUG_SYMBOLS = ("nnop_debug_set", "nnop_debug_dev_build", "nnop_debug_fwd_form", "nnop_debug_bwd_form",
-                 "nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex")
+                 "nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex", "nnop_debug_fwd_form_cap", "nnop_debug_bwd_form_cap")
 FWD_FORMS = {0: "fa_fwd_kernel", 1: "fa_fwd_split_kernel", 2: "fa_fwd_w64_kernel", 3: "fa_fwd_generic_kernel", 4: "fa_fwd_duo_kernel"}
+FWD_FORMS_CAP = {0: "fa_fwd_cap_kernel", 3: "fa_fwd_generic_cap_kernel"}      # a capped call runs these two forms only
 # keys of nnop_debug_set == enum TuneKey (csrc/tuning.hpp)
 TUNE_KEYS = {"fwd_split": 0, "fwd_nw": 1, "fwd_w64": 2, "bwd_big7": 3, "norm_bwd_cap": 4, "bwd_nw": 5,
              "fwd_exact_scale": 6, "bwd_w64": 7, "bwd_stages": 8, "fwd_persist": 9, "bwd_persist": 10, "fwd_duo": 11, "fwd_persist_asc": 12, "bwd_narrow": 13, "fwd_causal_alt": 14}
@@ -155,6 +159,11 @@ def load():
     lib.nnop_fa_bwd_sinks.restype = C.c_int
     lib.nnop_fa_bwd_sinks.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       u8p, vp, C.c_size_t, vp]
+    lib.nnop_fa_fwd_softcap.restype = C.c_int
+    lib.nnop_fa_fwd_softcap.argtypes = [C.POINTER(FaDesc), op, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
+    lib.nnop_fa_bwd_softcap.restype = C.c_int
+    lib.nnop_fa_bwd_softcap.argtypes = [C.POINTER(FaDesc), op, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                        u8p, vp, C.c_size_t, vp]
     lib.nnop_llama_rope.restype = C.c_int
     lib.nnop_llama_rope.argtypes = [C.POINTER(RopeDesc), vp, vp, vp, vp, vp, vp, C.c_float, vp]
     lib.nnop_online_softmax.restype = C.c_int
@@ -193,6 +202,10 @@ def load():
         if hasattr(lib, name):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.POINTER(FaOpts), C.c_int, C.c_int]
+    for name in ("nnop_debug_fwd_form_cap", "nnop_debug_bwd_form_cap"):
+        if hasattr(lib, name):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.POINTER(FaOpts), C.c_float, C.c_int, C.c_int]
     _lib = lib
     return lib
 
@@ -244,10 +257,27 @@ def fa_opts(window=None, desc=None):
     return FaOpts(window_left=left, window_right=right)
 
 
-def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None) -> str:
-    """Name of the forward kernel the launcher picks for this problem (reporting only; csrc/nnop_debug.h)."""
+def fa_softcap(softcap=None):
+    """Logit soft-capping as the library takes it: 0.0 for None / 0 (no cap: exactly the call without one), else the cap as a
+    float.  A non-number is a TypeError; a negative or non-finite cap is refused by the library (NNOP_ERR_OPTS) -- and by
+    attention.py before any GPU use."""
+    if softcap is None:
+        return 0.0
+    if isinstance(softcap, bool) or not isinstance(softcap, numbers.Real):      # numpy's scalar types register as Real
+        raise TypeError(f"softcap must be None or a number, got {softcap!r}")
+    return float(softcap)
+
+
+def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None, softcap=None) -> str:
+    """Name of the forward kernel the launcher picks for this problem (reporting only; csrc/nnop_debug.h).  It names the form: a
+    call with sinks launches the form's `_sink_kernel` twin (fa_fwd_sink_kernel, fa_fwd_cap_sink_kernel, ...)."""
     opts = fa_opts(window)
-    if opts is None:
+    if fa_softcap(softcap) != 0.0:
+        code = load().nnop_debug_fwd_form_cap(C.byref(desc), C.byref(opts) if opts is not None else None, fa_softcap(softcap),
+                                              int(has_pair), int(has_mask))
+        if code >= 0:
+            return FWD_FORMS_CAP[code]
+    elif opts is None:
         code = load().nnop_debug_fwd_form(C.byref(desc), int(has_pair), int(has_mask))
     else:
         code = load().nnop_debug_fwd_form_ex(C.byref(desc), C.byref(opts), int(has_pair), int(has_mask))
@@ -256,10 +286,15 @@ def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, windo
     return FWD_FORMS[code]
 
 
-def bwd_kernels(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None):
-    """Names of the (dK/dV, dQ) kernels the launcher picks for this problem (reporting only; csrc/nnop_debug.h)."""
+def bwd_kernels(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None, softcap=None):
+    """Names of the (dK/dV, dQ) kernels the launcher picks for this problem (reporting only; csrc/nnop_debug.h).  It tells the w64
+    backward from the fa_bwd.hpp one and no more: the plain-HIP kernels (fa_bwd_generic_*) report as the latter, and a capped call
+    launches the same templates with the cap bit of MODE set (MODE 5, 6) or the plain-HIP `_cap_kernel` twins."""
     opts = fa_opts(window)
-    if opts is None:
+    if fa_softcap(softcap) != 0.0:
+        code = load().nnop_debug_bwd_form_cap(C.byref(desc), C.byref(opts) if opts is not None else None, fa_softcap(softcap),
+                                              int(has_pair), int(has_mask))
+    elif opts is None:
         code = load().nnop_debug_bwd_form(C.byref(desc), int(has_pair), int(has_mask))
     else:
         code = load().nnop_debug_bwd_form_ex(C.byref(desc), C.byref(opts), int(has_pair), int(has_mask))

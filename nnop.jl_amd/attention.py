@@ -142,9 +142,23 @@ def bwd_workspace_bytes(q, k, v, *, causal: bool, pair: bool = False) -> int:
     return int(f(C.byref(_desc(q, k, v, causal))))
 
 
-def _fwd_call(lib, opts, d, *args, sinks=None):
+def _softcap(softcap):
+    """The cap as the library takes it (0.0 = none).  A negative or non-finite cap raises what the library would answer,
+    NNOP_ERR_OPTS, before anything touches the GPU; a non-number is a TypeError."""
+    c = _lib.fa_softcap(softcap)
+    if not (c >= 0.0 and math.isfinite(c)):
+        raise NNopError(f"softcap must be a finite number >= 0 (0 or None: no cap), got {softcap!r}. "
+                        f"({_lib.strerror(_lib.NNOP_ERR_OPTS)})", _lib.NNOP_ERR_OPTS)
+    return c
+
+
+def _fwd_call(lib, opts, d, *args, sinks=None, softcap=0.0):
     """nnop_fa_fwd, or nnop_fa_fwd_ex when there are per-call options (window=None issues exactly the old call), or
-    nnop_fa_fwd_sinks with sinks (a fp32 tensor; sinks=None issues exactly the call without them)"""
+    nnop_fa_fwd_sinks with sinks (a fp32 tensor; sinks=None issues exactly the call without them), or nnop_fa_fwd_softcap
+    with a cap (softcap=0.0 issues exactly the call without one)"""
+    if softcap != 0.0:
+        return lib.nnop_fa_fwd_softcap(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks),
+                                       C.c_float(softcap), *args)
     if sinks is not None:
         return lib.nnop_fa_fwd_sinks(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks), *args)
     if opts is None:
@@ -152,7 +166,10 @@ def _fwd_call(lib, opts, d, *args, sinks=None):
     return lib.nnop_fa_fwd_ex(C.byref(d), C.byref(opts), *args)
 
 
-def _bwd_call(lib, opts, d, *args, sinks=None, dsinks=None):
+def _bwd_call(lib, opts, d, *args, sinks=None, dsinks=None, softcap=0.0):
+    if softcap != 0.0:
+        return lib.nnop_fa_bwd_softcap(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks), _ptr(dsinks),
+                                       C.c_float(softcap), *args)
     if sinks is not None:
         return lib.nnop_fa_bwd_sinks(C.byref(d), C.byref(opts) if opts is not None else None, _ptr(sinks), _ptr(dsinks),
                                      *args)
@@ -175,36 +192,38 @@ def _sinks_f32(sinks, q):
     return sinks.detach().to(torch.float32).contiguous()
 
 
-def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
+def fa_fwd_into(o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None, softcap=None):
     """Raw ``nnop_fa_fwd`` into caller-owned, preallocated outputs (the C ABI's ownership model:
     the caller allocates everything).  No checks beyond the library's own; contiguous tensors only.
-    Used by bench.py so that a timed step is exactly one library call.  ``window``, ``sinks``: see flash_attention
+    Used by bench.py so that a timed step is exactly one library call.  ``window``, ``sinks``, ``softcap``: see flash_attention
     (``sinks`` here: a contiguous fp32 [QH] tensor, passed as it is)."""
     d = _desc(q, k, v, causal)
     st = _fwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                   _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks)
+                   _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks, softcap=_softcap(softcap))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
 def fa_bwd_into(dq, dk, dv, dpair, ws, dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None,
-                sinks=None, dsinks=None):
+                sinks=None, dsinks=None, softcap=None):
     """Raw ``nnop_fa_bwd`` into caller-owned outputs and workspace (see fa_fwd_into).  With ``sinks``, ``dsinks`` is a
     caller-owned fp32 [QH] tensor that receives their gradient."""
     d = _desc(q, k, v, causal)
     st = _bwd_call(_lib.load(), _lib.fa_opts(window, d), d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
                    _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                   _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q), sinks=sinks, dsinks=dsinks)
+                   _ptr(ws), C.c_size_t(ws.numel() * ws.element_size()), _stream(q), sinks=sinks, dsinks=dsinks,
+                   softcap=_softcap(softcap))
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
 
 
-def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
+def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None, softcap=None):
     """``NNop._flash_attention`` (src/attention.jl:133-177): returns ``(o, ms, ls)``.
 
-    Asynchronous on the current torch stream, like the reference's KA launch.  ``window``, ``sinks``: see flash_attention
-    (with sinks, ``ms`` and ``ls`` include the sink column).
+    Asynchronous on the current torch stream, like the reference's KA launch.  ``window``, ``sinks``, ``softcap``: see
+    flash_attention (with sinks, ``ms`` and ``ls`` include the sink column; with a cap they are those of the capped logits).
     """
+    softcap = _softcap(softcap)
     lib = _lib.load()
     opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
@@ -222,15 +241,18 @@ def _flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window
         ms = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :167
         ls = torch.empty((B, QH, QL), dtype=q.dtype, device=q.device)     # KA.allocate     :168
         st = _fwd_call(lib, opts, d, _ptr(o), _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v),
-                       _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks)
+                       _ptr(pair), _ptr(kpad_mask), _stream(q), sinks=sinks, softcap=softcap)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
     return o, ms, ls
 
 
-def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
+def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None,
+                         softcap=None):
     """``NNop.∇flash_attention`` (src/attention_bwd.jl:199-275): returns ``(dq, dk, dv, dpair|None)``, and with ``sinks``
-    ``(dq, dk, dv, dpair|None, dsinks)`` (dsinks: fp32 [QH]).  ``window``, ``sinks``: the forward's (see flash_attention)."""
+    ``(dq, dk, dv, dpair|None, dsinks)`` (dsinks: fp32 [QH]).  ``window``, ``sinks``, ``softcap``: the forward's (see
+    flash_attention)."""
+    softcap = _softcap(softcap)
     lib = _lib.load()
     opts = _lib.fa_opts(window)
     _check_inputs(q, k, v, pair, kpad_mask)
@@ -261,7 +283,7 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
         dpair = torch.empty_like(pair) if pair is not None else None
         dsinks = torch.empty_like(sinks) if sinks is not None else None
         nbytes = small = int(lib.nnop_fa_bwd_workspace_bytes(C.byref(d)))
-        if nbytes != 0 and pair is not None and opts is None:
+        if nbytes != 0 and pair is not None and opts is None and softcap == 0.0:
             # staged pair-bias path: two head-major bias-sized scratch matrices on top (the library returns the small size
             # where that path does not exist: plain-HIP embedding dims, too many heads for its LDS block)
             nbytes = max(nbytes, int(lib.nnop_fa_bwd_workspace_bytes_pair(C.byref(d))))
@@ -277,7 +299,7 @@ def grad_flash_attention(dO, o, ms, ls, q, k, v, pair=None, *, causal: bool, kpa
             ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
         st = _bwd_call(lib, opts, d, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dpair), _ptr(dO), _ptr(o),
                        _ptr(ms), _ptr(ls), _ptr(q), _ptr(k), _ptr(v), _ptr(pair), _ptr(kpad_mask),
-                       _ptr(ws), C.c_size_t(nbytes), _stream(q), sinks=sinks, dsinks=dsinks)
+                       _ptr(ws), C.c_size_t(nbytes), _stream(q), sinks=sinks, dsinks=dsinks, softcap=softcap)
     if st != _lib.NNOP_OK:
         _raise_status(st, q, k, v)
     if sinks is not None:
@@ -291,13 +313,15 @@ class _FlashAttentionFn(torch.autograd.Function):
     no tangent for kpad_mask."""
 
     @staticmethod
-    def forward(ctx, q, k, v, pair, kpad_mask, causal, window=None, sinks=None):
-        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks)
+    def forward(ctx, q, k, v, pair, kpad_mask, causal, window=None, sinks=None, softcap=None):
+        o, ms, ls = _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks,
+                                     softcap=softcap)
         ctx.save_for_backward(o, ms, ls, q, k, v, pair if pair is not None else torch.empty(0),
                               kpad_mask if kpad_mask is not None else torch.empty(0),
                               sinks if sinks is not None else torch.empty(0))
         ctx.has_pair, ctx.has_mask, ctx.causal, ctx.window = pair is not None, kpad_mask is not None, bool(causal), window
         ctx.has_sinks = sinks is not None
+        ctx.softcap = softcap                    # a plain float (or None): not differentiable
         return o
 
     @staticmethod
@@ -306,13 +330,13 @@ class _FlashAttentionFn(torch.autograd.Function):
         grads = grad_flash_attention(
             dO, o, ms, ls, q, k, v, pair if ctx.has_pair else None,
             causal=ctx.causal, kpad_mask=mask if ctx.has_mask else None, window=ctx.window,
-            sinks=sinks if ctx.has_sinks else None)
+            sinks=sinks if ctx.has_sinks else None, softcap=ctx.softcap)
         dq, dk, dv, dpair = grads[:4]
         dsinks = grads[4].to(sinks.dtype) if ctx.has_sinks else None     # in the sinks tensor's dtype
-        return dq, dk, dv, dpair, None, None, None, dsinks
+        return dq, dk, dv, dpair, None, None, None, dsinks, None
 
 
-def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None):
+def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=None, sinks=None, softcap=None):
     """``NNop.flash_attention(q, k, v, pair=nothing; causal, kpad_mask=nothing)``
     (src/attention_crc.jl:4-14).  ``causal`` is a required keyword, as in the reference.
     Returns ``o``; differentiable w.r.t. q, k, v, pair through the rrule above.
@@ -324,10 +348,16 @@ def flash_attention(q, k, v, pair=None, *, causal: bool, kpad_mask=None, window=
     ``sinks``: learned per-head attention sinks (gpt-oss), a 1-D ``[QH]`` float tensor on q's device, one logit per
     query head in the units of the scaled logits.  Each row's softmax gets one more column of logit ``sinks[h]`` and no
     value vector (concatenate, softmax, drop that column); causal, window, kpad_mask and pair act on the real keys only.
-    ``-inf`` means no sink for that head.  Differentiable: ``sinks.requires_grad`` gets a gradient in its own dtype."""
+    ``-inf`` means no sink for that head.  Differentiable: ``sinks.requires_grad`` gets a gradient in its own dtype.
+
+    ``softcap``: logit soft-capping (Gemma-2: 50, Grok-1: 30; flash-attn's ``softcap``), a float ``c > 0``: the scaled scores
+    become ``c * tanh(scale * q.k / c)`` before the pair bias is added (the bias and the sinks are not capped) and before the
+    masks and the softmax; fp32 arithmetic for every element type, differentiated through in the backward.  ``None`` or ``0``:
+    no cap, exactly the call without the argument.  A negative or non-finite value raises ``NNopError`` (NNOP_ERR_OPTS)."""
+    softcap = _softcap(softcap) or None
     if window is not None:
         window = tuple(window)
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (q, k, v, pair, sinks)):
-        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal), window, sinks)
-    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks)[0]
+        return _FlashAttentionFn.apply(q, k, v, pair, kpad_mask, bool(causal), window, sinks, softcap)
+    return _flash_attention(q, k, v, pair, causal=causal, kpad_mask=kpad_mask, window=window, sinks=sinks, softcap=softcap)[0]

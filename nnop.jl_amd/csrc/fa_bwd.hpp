@@ -68,6 +68,8 @@ struct BwdParams {
     int   persist = 0;   // fa_bwd_w64_kernel: blocks per workgroup of the persistent form (grid = 256 workgroups), 0 = one block per workgroup
     int   win_left = -1;    // the WIN = true kernels and the plain-HIP ones: sliding window (FaWindow, normalised), -1 = unbounded side
     int   win_right = -1;   // (behind the older fields: their kernel-argument offsets stay where they were)
+    float cap_ka = 0.f;     // the soft-capped kernels (MODE | kBwdCap, fa_bwd_generic_*_cap_kernel): the folded constants of SoftcapK
+    float cap_kb = 0.f;     // (fa_launch.hpp), behind the window for the same reason
 };
 
 // An fp32 row constant as three 16-bit terms (hi, mid, lo, 0 ...) whose sum is the value to ~24 bits: the form in which the dK/dV
@@ -234,15 +236,27 @@ constexpr int fa_bwd_dkdv_lds_bytes() {
            nbuf * (2 * BwdImgs<T, E>::both(BQ) + 2 * BQ * 4);
 }
 
+// Logit soft-capping (nnop_fa_bwd_softcap) is one more bit of MODE, on top of the masked modes 1 and 2 only: MODE 1 | kBwdCap = 5,
+// 2 | kBwdCap = 6.  The kernels of the calls without a cap are the instantiations with the bit clear: the same template arguments, hence
+// the same symbols, as before the cap existed, and every cap statement is behind `if constexpr (CAP)`.  With the bit set the score
+// accumulator starts at 0 instead of the row constant nl (the cap needs the raw q.k), the raw score is capped, the pair bias added, and
+// the row's nl subtracted in registers: x = kb * tanh(raw * scale / c) + pair * log2e + nl * c2, P = exp2(x); dS for the dQ / dK
+// products becomes P dP' (1 - tanh^2), dpair still receives P dP'.
+constexpr int kBwdCap = 4;
+constexpr int bwd_base_mode(int mode) { return mode & 3; }
+
 // MODE 0 plain / 1 masked (causal, key padding) / 2 masked + pair bias and dpair  (as in fa_fwd.hpp)
 // WIN (MODE 1 / 2): sliding window p.win_left / p.win_right -- the q tiles of a key block are bounded by it and the blocks that cross
 // a window edge take the per-element select.  WIN = false compiles to the code without a window.
 template <typename T, int E, int NW, int BQ, int MODE, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void fa_bwd_dkdv_kernel(const BwdParams p) {
-    constexpr bool kGeneral = MODE != 0;
-    static_assert(!WIN || (MODE == 1 || MODE == 2), "the window runs in the masked modes (direct pair path)");
-    constexpr bool kPair = MODE >= 2;
-    constexpr bool kStaged = MODE == 3;          // pair bias through head-major scratch + LDS tiles (pair_tile.hpp)
+    constexpr bool CAP = (MODE & kBwdCap) != 0;
+    constexpr int BM = bwd_base_mode(MODE);      // MODE without the cap bit
+    constexpr bool kGeneral = BM != 0;
+    static_assert(!WIN || (BM == 1 || BM == 2), "the window runs in the masked modes (direct pair path)");
+    static_assert(MODE < 8 && (!CAP || (WIN && (BM == 1 || BM == 2))), "the cap runs in the windowed instantiations of the masked modes");
+    constexpr bool kPair = BM >= 2;
+    constexpr bool kStaged = BM == 3;            // pair bias through head-major scratch + LDS tiles (pair_tile.hpp)
     using frag_t = typename Elem<T>::frag;
     using Imgs = BwdImgs<T, E>;
     using Row = typename Imgs::Row;
@@ -251,10 +265,10 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
     constexpr int KS = E / 16;
     constexpr int EB = (E + 31) / 32;
     constexpr int QB = BQ / 32;
-    constexpr bool kKRegs = fa_bwd_dkdv_kregs<T, E, MODE, NW>(), kVRegs = fa_bwd_dkdv_vregs<T, E, MODE>();
+    constexpr bool kKRegs = fa_bwd_dkdv_kregs<T, E, BM, NW>(), kVRegs = fa_bwd_dkdv_vregs<T, E, BM>();
     constexpr int KIMG_B = kKRegs ? 0 : Row::bytes(32 * NW), VIMG_B = kVRegs ? 0 : Row::bytes(32 * NW);
     constexpr int QIMG = Imgs::both(BQ);
-    constexpr bool kSingle = fa_bwd_dkdv_single<T, E, NW, MODE>();
+    constexpr bool kSingle = fa_bwd_dkdv_single<T, E, NW, BM>();
     constexpr int BUF = kSingle ? 0 : 2 * QIMG + 2 * BQ * 4;      // distance between the two buffers (0: one buffer)
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -431,7 +445,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                 const f32x4 a = *reinterpret_cast<const f32x4*>(rc + 32 * qb + 8 * g4 + 4 * h);
                 const f32x4 d = *reinterpret_cast<const f32x4*>(rc + BQ + 32 * qb + 8 * g4 + 4 * h);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { s[4 * g4 + j] = a[j]; dp[4 * g4 + j] = d[j]; }
+                for (int j = 0; j < 4; ++j) { s[4 * g4 + j] = CAP ? 0.f : a[j]; dp[4 * g4 + j] = d[j]; }
             }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
@@ -456,7 +470,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             int qmax = 0;
             float pv[16];                                                  // kStaged: this lane's 16 bias values
             if constexpr (kStaged) {
-                PairTile<T>::unpack_rows(pregs, smem + fa_bwd_dkdv_lds_bytes<T, E, NW, BQ, MODE>() + wave * PairTile<T>::kBytes, lane, pv);
+                PairTile<T>::unpack_rows(pregs, smem + fa_bwd_dkdv_lds_bytes<T, E, NW, BQ, BM>() + wave * PairTile<T>::kBytes, lane, pv);
             } else if constexpr (kPair) {
                 pbase = (const T*)p.pair + (((size_t)b * p.KL + key_c) * p.QL + q0) * p.QH + qh;
                 qmax = p.QL - 1 - q0;                                      // last in-range local query row
@@ -468,8 +482,14 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             auto p_ds = [&](auto masked) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    float x = s[i] * c2;
                     const int lrow = acc_row(i, h);
+                    float x, th = 0.f;
+                    if constexpr (CAP) {                                     // raw score -> cap -> + the row's nl (LDS, one per accumulator row)
+                        th = cap_tanh(s[i], p.cap_ka);
+                        x = __builtin_fmaf(rc[32 * qb + lrow], c2, th * p.cap_kb);
+                    } else {
+                        x = s[i] * c2;
+                    }
                     if constexpr (kStaged) {
                         x += pv[i] * kLog2e;
                     } else if constexpr (kPair) {
@@ -490,6 +510,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                     }
                     s[i] = pr;
                     ds[i] = pr * dp[i];
+                    if constexpr (CAP) ds[i] *= __builtin_fmaf(-th, th, 1.f);
                 }
             };
             if constexpr (kPair && !kStaged) {
@@ -568,10 +589,13 @@ constexpr int fa_bwd_dq_lds_bytes() {
 // WIN (MODE 1 / 2): sliding window -- the key tiles are bounded as in the forward; `need_mask` covers the window edges.
 template <typename T, int E, int NW, int BK, int MODE, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void fa_bwd_dq_kernel(const BwdParams p) {
-    constexpr bool kGeneral = MODE != 0;
-    static_assert(!WIN || (MODE == 1 || MODE == 2), "the window runs in the masked modes (direct pair path)");
-    constexpr bool kPair = MODE >= 2;
-    constexpr bool kStaged = MODE == 3;          // pair bias / dS through head-major scratch + LDS tiles (pair_tile.hpp)
+    constexpr bool CAP = (MODE & kBwdCap) != 0;  // logit soft-capping, see kBwdCap
+    constexpr int BM = bwd_base_mode(MODE);
+    constexpr bool kGeneral = BM != 0;
+    static_assert(!WIN || (BM == 1 || BM == 2), "the window runs in the masked modes (direct pair path)");
+    static_assert(MODE < 8 && (!CAP || (WIN && (BM == 1 || BM == 2))), "the cap runs in the windowed instantiations of the masked modes");
+    constexpr bool kPair = BM >= 2;
+    constexpr bool kStaged = BM == 3;            // pair bias / dS through head-major scratch + LDS tiles (pair_tile.hpp)
     using frag_t = typename Elem<T>::frag;
     using Imgs = BwdImgs<T, E>;
     using Row = typename Imgs::Row;
@@ -580,7 +604,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
     constexpr int KS = E / 16;
     constexpr int EB = (E + 31) / 32;
     constexpr int KB = BK / 32;
-    constexpr bool kQRegs = fa_bwd_dq_qregs<T, E, MODE>();     // else Q, dO fragments come from LDS row images
+    constexpr bool kQRegs = fa_bwd_dq_qregs<T, E, BM>();       // else Q, dO fragments come from LDS row images
     constexpr int QIMG = kQRegs ? 0 : Row::bytes(32 * NW);
     constexpr int KIMG = Imgs::both(BK);
     constexpr bool kSingle = fa_bwd_single<T, E, NW>() && !kQRegs;
@@ -636,7 +660,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
         if (mp) {
             // variable sequence length: validity words in LDS + stop after the tile holding the last valid key (as the
             // forward does); no valid key at all -> 0 tiles -> dQ = 0
-            uint64_t* vbits = reinterpret_cast<uint64_t*>(smem + (fa_bwd_dq_lds_bytes<T, E, NW, BK, MODE>() - 8 * kMaxMaskTilesBwd));
+            uint64_t* vbits = reinterpret_cast<uint64_t*>(smem + (fa_bwd_dq_lds_bytes<T, E, NW, BK, BM>() - 8 * kMaxMaskTilesBwd));
             int* slot = reinterpret_cast<int*>(smem);
             const int nk = n_tiles * BK < p.KL ? n_tiles * BK : p.KL;
             const int last = kpad_scan(mp, p.KL, nk, vbits, kMaxMaskTilesBwd, slot, tid, NT);
@@ -719,7 +743,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
             if (mp) {
                 if ((t * BK) >> 6 < kMaxMaskTilesBwd) {
                     valid &= kpad_tile_bits<BK>(reinterpret_cast<const uint64_t*>(
-                        smem + (fa_bwd_dq_lds_bytes<T, E, NW, BK, MODE>() - 8 * kMaxMaskTilesBwd)), t);
+                        smem + (fa_bwd_dq_lds_bytes<T, E, NW, BK, BM>() - 8 * kMaxMaskTilesBwd)), t);
                 } else {
                     const int kk = k0 + lane;
                     const bool lv = (lane < BK && kk < p.KL) ? (mp[kk] != 0) : false;
@@ -749,7 +773,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                 }
                 f32x16 s, dp;
 #pragma unroll
-                for (int i = 0; i < 16; ++i) { s[i] = nlq; dp[i] = ndl; }
+                for (int i = 0; i < 16; ++i) { s[i] = CAP ? 0.f : nlq; dp[i] = ndl; }
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     frag_t qfr, dofr;
@@ -769,7 +793,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                 float pv[16];                                              // kStaged: this lane's 16 bias values
                 char* ptile = nullptr;
                 if constexpr (kStaged) {
-                    ptile = smem + fa_bwd_dq_lds_bytes<T, E, NW, BK, MODE>() + wave * PairTile<T>::kBytes;
+                    ptile = smem + fa_bwd_dq_lds_bytes<T, E, NW, BK, BM>() + wave * PairTile<T>::kBytes;
                     PairTile<T>::unpack(pregs, ptile, lane, pv);
                 } else if constexpr (kPair) {
                     kstride = p.QL * p.QH;
@@ -783,7 +807,13 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                 auto p_ds = [&](auto masked) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        float x = s[i] * c2;
+                        float x, th = 0.f;
+                        if constexpr (CAP) {                                 // raw score -> cap -> + this lane's nl
+                            th = cap_tanh(s[i], p.cap_ka);
+                            x = __builtin_fmaf(nlq, c2, th * p.cap_kb);
+                        } else {
+                            x = s[i] * c2;
+                        }
                         if constexpr (kStaged) x += pv[i] * kLog2e;
                         bool ok = true;
                         if constexpr (decltype(masked)::value) {
@@ -808,6 +838,7 @@ __global__ __launch_bounds__(NW * 64, (sizeof(T) == 4 && E > 64) ? 1 : 2) void f
                             const int klr = 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h;
                             if (klr <= kmax && qi < p.QL) dpbase[klr * kstride] = from_f32<T>(ds[i]);
                         }
+                        if constexpr (CAP) ds[i] *= __builtin_fmaf(-th, th, 1.f);      // (behind the dpair store: dpair = dS, not dS')
                     }
                 };
                 if constexpr (kPair && !kStaged) {

@@ -38,7 +38,8 @@ static inline int bwd_causal_alt(const nnop_fa_desc& d, long long n_wg, long lon
 
 template <typename T, int E, int NW, int BQ, int MODE, bool WIN = false>
 static int launch_dkdv(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
-    constexpr int lds = fa_bwd_dkdv_lds_bytes<T, E, NW, BQ, MODE>() + (MODE == 3 ? NW * PairTile<T>::kBytes : 0);
+    constexpr int BM = bwd_base_mode(MODE);                  // (MODE may carry the cap bit, fa_bwd.hpp kBwdCap)
+    constexpr int lds = fa_bwd_dkdv_lds_bytes<T, E, NW, BQ, BM>() + (BM == 3 ? NW * PairTile<T>::kBytes : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = fa_bwd_dkdv_kernel<T, E, NW, BQ, MODE, WIN>;
     static unsigned long long lds_done = 0;
@@ -49,14 +50,15 @@ static int launch_dkdv(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s)
     if (n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     pk.n_wg = (int)n_wg;
     if (n_wg * fa_bwd_split<T, E>() > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    pk.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.kh * d.batch, 1, pk.n_blk, MODE >= 2);
+    pk.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.kh * d.batch, 1, pk.n_blk, BM >= 2);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg * fa_bwd_split<T, E>())), dim3(NW * 64), lds, s, pk);   // (fp32 E = 256: every block once per column slice)
     return NNOP_OK;
 }
 
 template <typename T, int E, int NW, int BK, int MODE, bool WIN = false>
 static int launch_dq(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
-    constexpr int lds = fa_bwd_dq_lds_bytes<T, E, NW, BK, MODE>() + (MODE == 3 ? NW * PairTile<T>::kBytes : 0);
+    constexpr int BM = bwd_base_mode(MODE);
+    constexpr int lds = fa_bwd_dq_lds_bytes<T, E, NW, BK, BM>() + (BM == 3 ? NW * PairTile<T>::kBytes : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = fa_bwd_dq_kernel<T, E, NW, BK, MODE, WIN>;
     static unsigned long long lds_done = 0;
@@ -67,7 +69,7 @@ static int launch_dq(const nnop_fa_desc& d, const BwdParams& p, hipStream_t s) {
     if (n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     pq.n_wg = (int)n_wg;
     if (n_wg * fa_bwd_split<T, E>() > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    pq.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, pq.n_blk, MODE >= 2);
+    pq.causal_alt = WIN ? 0 : bwd_causal_alt(d, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, pq.n_blk, BM >= 2);
     hipLaunchKernelGGL(kern, dim3((unsigned)(n_wg * fa_bwd_split<T, E>())), dim3(NW * 64), lds, s, pq);
     return NNOP_OK;
 }
@@ -135,7 +137,7 @@ static inline bool bwd_w64_narrow(const nnop_fa_desc& d, int kind) {
     return small_grid_prefers_32_row_waves(len, (long long)hd * d.batch, d.causal != 0);
 }
 // bit 0: dK/dV runs fa_bwd_w64_kernel, bit 1: dQ does (knob kTuneBwdW64: 0 never, 1 both, 2 dK/dV only, 3 dQ only, 4 both with the
-// preprocess launch kept, auto = both).  Never with a sliding window (fa_bwd.hpp WIN only).
+// preprocess launch kept, auto = both).  Never with a sliding window (fa_bwd.hpp WIN only) or a soft cap (`windowed` covers both).
 static inline int bwd_w64_forms(const nnop_fa_desc& d, bool has_pair, bool ws_aligned16, bool windowed = false) {
     if (has_pair || windowed) return 0;
     const int t = tune_get(kTuneBwdW64);
@@ -162,6 +164,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.causal = d.causal ? 1 : 0;
     if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
+    if constexpr ((MODE & kBwdCap) != 0) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)E), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
     p.scale = (float)(1.0 / sqrt((double)E));
     p.n_blk = 0; p.n_wg = 0;
     p.pair_a = nullptr; p.dpair_s = nullptr;
@@ -205,6 +208,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     // 3. dK, dV
     auto run_dkdv = [&]() -> int {
         if constexpr (WIN) return launch_dkdv<T, E, C::NW_KV, C::BQ, MODE, true>(d, p, s);     // the one windowed shape
+        else {
         int st = NNOP_OK;
         bool done = false;
         if constexpr (MODE <= 1 && sizeof(T) == 2 && (E == 64 || E == 128 || E == 256)) {
@@ -228,10 +232,12 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
         }
         if (!done) st = launch_dkdv<T, E, C::NW_KV, C::BQ, MODE>(d, p, s);
         return st;
+        }
     };
     // 4. dQ
     auto run_dq = [&]() -> int {
         if constexpr (WIN) return launch_dq<T, E, C::NW_Q, C::BK, MODE, true>(d, p, s);
+        else {
         int st = NNOP_OK;
         bool done = false;
         if constexpr (MODE <= 1 && sizeof(T) == 2 && (E == 64 || E == 128 || E == 256)) {
@@ -264,6 +270,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
         }
         if (!done) st = launch_dq<T, E, C::NW_Q, C::BK, MODE>(d, p, s);
         return st;
+        }
     };
     if (p.fused) {
         if (stages & 4) { const int st = run_dq(); if (st != NNOP_OK) return st; }
@@ -283,6 +290,12 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
 
 template <typename T, int E>
 static int launch_bwd_e(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) {
+    if (a.softcap != 0.f) {
+        // logit soft-capping: the cap bit on the windowed bodies of fa_bwd.hpp (without a window their bounds stay -1); with a pair
+        // bias always the direct path, whatever the workspace holds
+        if constexpr (sizeof(T) == 4 && E == 256) return NNOP_ERR_EMB_UNSUPPORTED;      // (launch_bwd: the plain-HIP kernels)
+        else return a.pair ? launch_bwd_cfg<T, E, 2 | kBwdCap, true>(d, a, s) : launch_bwd_cfg<T, E, 1 | kBwdCap, true>(d, a, s);
+    }
     if (a.win.on()) {
         // sliding window: the WIN bodies of fa_bwd.hpp; with a pair bias always the direct path (MODE 2), never the staged scratch
         if constexpr (sizeof(T) == 4 && E == 256) {
@@ -322,6 +335,8 @@ template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const
     p.causal = d.causal ? 1 : 0;
     p.win_left = a.win.left; p.win_right = a.win.right;
     p.scale = (float)(1.0 / sqrt((double)d.emb));
+    const bool capped = a.softcap != 0.f;
+    if (capped) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
     p.n_blk = 0; p.n_wg = 0;
     p.pair_a = nullptr; p.dpair_s = nullptr; p.QLp = p.KLp = 0;
     const long long gq = (n_rows + 3) / 4, gk = (n_krows + 3) / 4;
@@ -331,8 +346,13 @@ template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const
         if (hipMemsetAsync(p.dpair, 0, bytes, s) != hipSuccess) { (void)hipGetLastError(); return NNOP_ERR_HIP; }
     }
     hipLaunchKernelGGL((fa_bwd_generic_pre_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-    hipLaunchKernelGGL((fa_bwd_generic_dq_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-    hipLaunchKernelGGL((fa_bwd_generic_dkdv_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
+    if (capped) {
+        hipLaunchKernelGGL((fa_bwd_generic_dq_cap_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
+        hipLaunchKernelGGL((fa_bwd_generic_dkdv_cap_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
+    } else {
+        hipLaunchKernelGGL((fa_bwd_generic_dq_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
+        hipLaunchKernelGGL((fa_bwd_generic_dkdv_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
+    }
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
@@ -340,7 +360,8 @@ template <typename T> int launch_bwd(const nnop_fa_desc& d, const BwdArgs& a, hi
     if constexpr (sizeof(T) == 2) {
         if (d.emb == 256) return launch_bwd_e<T, 256>(d, a, s);     // tiled kernels, 2 waves, single-buffered (see launch_fwd)
     } else {
-        if (d.emb == 256 && !a.pair) return launch_bwd_e<T, 256>(d, a, s);     // fp32: tiled kernels, 1 wave (no pair-bias mode: plain HIP)
+        // fp32: tiled kernels, 1 wave (no pair-bias mode: plain HIP; a soft cap likewise -- that body spills ~100 registers as it is)
+        if (d.emb == 256 && !a.pair && a.softcap == 0.f) return launch_bwd_e<T, 256>(d, a, s);
     }
     if (emb_generic(d.emb)) return launch_bwd_generic<T>(d, a, s);
     switch (d.emb) {

@@ -110,6 +110,14 @@ NNOP_DEV float sink_merge(float s2, float& m, float& l, float& mt) {
     return a;
 }
 
+// Logit soft-capping (nnop_fa_fwd_softcap): z = c * tanh(s * scale / c).  gfx950 has no tanh instruction; it is built from the hardware
+// exp2 and reciprocal: tanh(u) = 1 - 2 / (exp(2u) + 1).  `raw` is the unscaled q.k accumulator and ka = scale / c * 2 log2(e) is folded by
+// the launcher (SoftcapK), so that exp(2u) = exp2(raw * ka).  Saturates cleanly: exp2 -> +inf gives 1, exp2 -> 0 gives -1; no NaN for
+// finite input.  Absolute error ~2 ulp of 1 (1.2e-7) everywhere, i.e. ~c * 1.2e-7 on the capped logit.
+NNOP_DEV float cap_tanh(float raw, float ka) {
+    return 1.f - 2.f * __builtin_amdgcn_rcpf(fast_exp2(raw * ka) + 1.f);
+}
+
 // Force a register-resident value to have LANDED here: the compiler must insert the s_waitcnt for
 // the load that produces it at this point, not at its first use.  Used before a pipelined loop for
 // loads issued ahead of it: vmcnt retires in order, so a wait left inside the loop for an OLD load

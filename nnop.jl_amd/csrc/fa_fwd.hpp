@@ -98,6 +98,10 @@ struct FwdParams {
     // the SINK = true instantiations of every form: learned per-head attention sinks, fp32 [QH], merged in the epilogue (sink_merge).
     // Behind the window for the same reason.
     const float* sinks = nullptr;
+    // the CAP = true instantiations (fa_fwd_cap_kernel, fa_fwd_cap_sink_kernel) and fa_fwd_generic_cap_*: logit soft-capping, the two
+    // folded constants of SoftcapK (fa_launch.hpp).  Behind the sinks for the same reason.
+    float cap_ka = 0.f;
+    float cap_kb = 0.f;
 #ifdef NNOP_DEV_BUILD
     int   stagger = 0;       // experiment: s_sleep units for the odd co-resident workgroup (0 = off)
 #endif
@@ -112,8 +116,12 @@ struct FwdParams {
 // edge, the diagonal, KL or a key-padding word (tile_needs_mask).  WIN = false compiles to the code without a window.
 // SINK: learned attention sinks (p.sinks, non-null), merged in the epilogue.  One text, fa_fwd_kernel.inc, two kernels: fa_fwd_kernel
 // (SINK = false: the sink code compiles away) for the calls without sinks, fa_fwd_sink_kernel for the calls with them.
+// CAP (MODE 1 / 2 only, instantiated with WIN = true only): logit soft-capping, x = c * tanh(s * scale / c) (+ pair), applied in finish_x
+// to the raw accumulators; the tile is then in log2 units, as with a pair bias.  Two more kernels of the same text, fa_fwd_cap_kernel
+// and fa_fwd_cap_sink_kernel: the kernels of the calls without a cap keep their names and their code.
 #define NNOP_FWD_NAME fa_fwd_kernel
 #define NNOP_FWD_SINK false
+#define NNOP_FWD_CAP false
 #include "fa_fwd_kernel.inc"
 #undef NNOP_FWD_NAME
 #undef NNOP_FWD_SINK
@@ -122,6 +130,19 @@ struct FwdParams {
 #include "fa_fwd_kernel.inc"
 #undef NNOP_FWD_NAME
 #undef NNOP_FWD_SINK
+#undef NNOP_FWD_CAP
+#define NNOP_FWD_CAP true
+#define NNOP_FWD_NAME fa_fwd_cap_kernel
+#define NNOP_FWD_SINK false
+#include "fa_fwd_kernel.inc"
+#undef NNOP_FWD_NAME
+#undef NNOP_FWD_SINK
+#define NNOP_FWD_NAME fa_fwd_cap_sink_kernel
+#define NNOP_FWD_SINK true
+#include "fa_fwd_kernel.inc"
+#undef NNOP_FWD_NAME
+#undef NNOP_FWD_SINK
+#undef NNOP_FWD_CAP
 
 
 // LDS bytes the kernel needs: K ring of 2 + V ring of 2 + one scratch slot + (key padding) one 64-bit validity

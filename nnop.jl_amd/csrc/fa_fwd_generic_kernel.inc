@@ -1,9 +1,11 @@
 // fa_fwd_generic_kernel.inc -- the body of fa_fwd_generic_kernel (fa_generic.hpp).
-// Included twice by fa_generic.hpp: NNOP_GENERIC_NAME = the kernel's name, NNOP_GENERIC_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false).
+// Included four times by fa_generic.hpp: NNOP_GENERIC_NAME = the kernel's name, NNOP_GENERIC_SINK = learned attention sinks merged in the epilogue (a
+// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false), NNOP_GENERIC_CAP =
+// logit soft-capping with the runtime constants p.cap_ka / p.cap_kb (kernels of their own for the same reason).
 template <typename T>
 __global__ __launch_bounds__(256) void NNOP_GENERIC_NAME(const FwdParams p, int E, long long n_rows) {
     constexpr bool SINK = NNOP_GENERIC_SINK;
+    constexpr bool CAP = NNOP_GENERIC_CAP;
     __shared__ float qs_all[4][kGenericMaxE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + wave;
@@ -28,7 +30,9 @@ __global__ __launch_bounds__(256) void NNOP_GENERIC_NAME(const FwdParams p, int 
         const int k = k0 + lane;
         const bool valid = k < kend && (!mp || mp[k] != 0);
         const int kc = k < p.KL ? k : p.KL - 1;
-        float s = dot_lds(qs, kb + (size_t)kc * E, E) * p.scale;
+        float s = dot_lds(qs, kb + (size_t)kc * E, E);
+        if constexpr (CAP) s = cap_tanh(s, p.cap_ka) * (p.cap_kb * kLn2);     // c * tanh(s * scale / c), before the bias
+        else s *= p.scale;
         if (p.pair) s += to_f32(((const T*)p.pair)[(((size_t)b * p.KL + kc) * p.QL + qi) * p.QH + qh]);
         if (!valid) s = -INFINITY;
         const float m_new = fmaxf(m, wave_max64(s));

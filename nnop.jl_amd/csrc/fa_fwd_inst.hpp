@@ -26,7 +26,7 @@ static inline int dev_env_int(const char* name, int dflt) {
 }
 #endif
 
-template <typename T, int E, int NW, int MODE, int QB, bool WIN = false>
+template <typename T, int E, int NW, int MODE, int QB, bool WIN = false, bool CAP = false>
 static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     // 64-key tiles, except the E = 128 pair-bias body (register budget) and fp32 E = 128
     // (LDS: 2 x (K + V) x 64 keys x 512 B = 128 KiB would leave one workgroup per CU)
@@ -34,7 +34,10 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     constexpr int lds = fa_fwd_lds_bytes<T, E, BK>();
     static_assert(lds <= 160 * 1024, "LDS budget (160 KiB per CU on gfx950)");
     // learned sinks: the SINK = true instantiation (the code of the calls without them stays as it is)
-    auto kern = a.sinks ? fa_fwd_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
+    // a soft cap: the CAP = true kernels (fa_fwd.hpp), likewise
+    void (*kern)(const FwdParams);
+    if constexpr (CAP) kern = a.sinks ? fa_fwd_cap_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_cap_kernel<T, E, NW, BK, MODE, QB, WIN>;
+    else kern = a.sinks ? fa_fwd_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
     static unsigned long long lds_done[2] = {0, 0};
     if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
@@ -57,6 +60,7 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     p.causal_alt = (!WIN && MODE != 2 && (E <= 64 || (E == 128 && sizeof(T) == 4 && NW == 4)))
                        ? causal_alt_run(d.causal != 0, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, p.n_qblk) : 0;
     if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
+    if constexpr (CAP) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)E), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
     int lds_launch = lds;
 #ifdef NNOP_DEV_BUILD
     // experiments (make DEV=1 only): de-phase co-resident workgroups; pad LDS to limit workgroups per CU
@@ -207,7 +211,8 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
     const int E = d.emb;
     // the early exits of launch_fwd: embedding dims outside the tiled set (16-bit E = 256 runs the 32-row tiled kernel)
     if (E != 256 && emb_generic(E)) return kFormGeneric;
-    // a sliding window (FaWindow::on) exists in the 32-row kernel only (fa_fwd.hpp WIN), not in the duo / w64 / split forms
+    // a sliding window (FaWindow::on) exists in the 32-row kernel only (fa_fwd.hpp WIN), not in the duo / w64 / split forms; so does a
+    // soft cap (CAP), which callers report as `windowed`
     if (windowed) return kFormRow32;
     const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
     if (b16 && E == 256) {
@@ -277,13 +282,18 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
 
 template <typename T, int E>
 static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
-    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr, a.win.on());
-    const int form = fwd_form_of(d, mode, a.win.on());
+    const bool capped = a.softcap != 0.f;
+    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr, a.win.on() || capped);
+    if (capped) {
+        // logit soft-capping: the CAP instantiations of the windowed body, same shape; without a window its bounds stay -1 (unbounded)
+        return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true, true>(d, a, s);
+    }
     if (a.win.on()) {
         // sliding window: the 32-row kernel's WIN body, 4 waves (128-row workgroups: a block's rows span less of the window, and a
         // windowed grid has as many blocks as the causal one)
         return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true>(d, a, s);
     }
+    const int form = fwd_form_of(d, mode, false);
     // Workgroup shape of the 32-row form: 8 waves x 32 rows (256-row workgroups) when that still yields >= one
     // workgroup per CU, else 4 waves x 32 rows so that small problems spread over more CUs.
     const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
@@ -367,6 +377,12 @@ template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const
     const long long n_rows = (long long)d.batch * d.qh * d.ql;
     const long long grid = (n_rows + 3) / 4;
     if (grid > 0x7fffffffLL) return NNOP_ERR_SHAPE;
+    if (a.softcap != 0.f) {
+        const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap);
+        p.cap_ka = ck.ka; p.cap_kb = ck.kb;
+        if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_cap_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
+        else hipLaunchKernelGGL((fa_fwd_generic_cap_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
+    } else
     if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
     else hipLaunchKernelGGL((fa_fwd_generic_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;

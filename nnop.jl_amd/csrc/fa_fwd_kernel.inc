@@ -1,15 +1,21 @@
 // fa_fwd_kernel.inc -- the body of fa_fwd_kernel (fa_fwd.hpp).
-// Included twice by fa_fwd.hpp: NNOP_FWD_NAME = the kernel's name, NNOP_FWD_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false).
+// Included four times by fa_fwd.hpp: NNOP_FWD_NAME = the kernel's name, NNOP_FWD_SINK = learned attention sinks merged in the epilogue (a
+// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false), NNOP_FWD_CAP =
+// logit soft-capping in finish_x (kernels of their own for the same reason).
 template <typename T, int E, int NW, int BK, int MODE, int QB, bool WIN = false>
 __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) ? 1 : 2) void NNOP_FWD_NAME(const FwdParams p) {
     constexpr bool SINK = NNOP_FWD_SINK;
+    constexpr bool CAP = NNOP_FWD_CAP;
     using frag_t = typename Elem<T>::frag;
     using KImg   = RowImg<T, E>;
     using VImg   = ColImg<T, E>;
     constexpr bool kGeneral = MODE != 0;
     constexpr bool kPair = MODE == 2;
     static_assert(!WIN || kGeneral, "the window runs in the masked modes");
+    // CAP rides on the WIN body (one tile per interval: at E = 128 the masked body is at its register limit, see kPipe, and the cap's
+    // transcendentals want the registers the second score tile of the pipelined body would hold); without a window the bounds are -1
+    static_assert(!CAP || WIN, "the cap runs in the windowed instantiations");
+    constexpr bool kLog2Tile = kPair || CAP;    // finish_x leaves the tile in log2 units (scaled, capped, biased): exp2(x - m) follows
     constexpr int NT  = NW * 64;
     constexpr int KS  = E / 16;                 // contraction steps of Q K^T
     constexpr int KB  = BK / 32;                // 32-key blocks per kv tile
@@ -298,13 +304,14 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
         return kGeneral && (valid != kFull || (p.causal && t * BK + BK - 1 > q0w));
     };
     // mask (-> -inf) / bias tile t of query block z in place and return its row max in log2 units (both halves).
-    // Plain / masked: logits stay in raw units; kPair: they become log2 units (s*c2 + pair*log2e).
+    // Plain / masked: logits stay in raw units; kPair: they become log2 units (s*c2 + pair*log2e); CAP: log2 units as well,
+    // kb * tanh(s * scale / c) (+ pair*log2e) -- the cap acts on the scaled score alone, before the bias.
     auto finish_x = [&](auto masked, int z, f32x16 (&s)[KB], int t, uint64_t valid) -> float {
         constexpr bool MASKED = decltype(masked)::value;
         if constexpr (WIN) t += t0;
         const int k0 = t * BK;
         float mxp[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // 4 independent chains
-        if constexpr (MASKED || kPair) {
+        if constexpr (MASKED || kLog2Tile) {
             // pair bias [B][KL][QL][QH]: one 64-bit base per (tile, lane), 32-bit element offsets, addresses clamped
             // into the tensor (no divergent branch around the loads), masked-out logits dropped by the select below
             const T* pbase = nullptr;
@@ -332,10 +339,12 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
                         }
                     }
                     float x = s[kb][i];
+                    if constexpr (CAP) x = cap_tanh(x, p.cap_ka) * p.cap_kb;
                     if constexpr (kPair) {
                         int kl = 32 * kb + lr + 4 * h;
                         kl = kl < kmax ? kl : kmax;
-                        x = __builtin_fmaf(x, c2, to_f32(pbase[kl * kstride]) * kLog2e);
+                        if constexpr (CAP) x = __builtin_fmaf(to_f32(pbase[kl * kstride]), kLog2e, x);
+                        else x = __builtin_fmaf(x, c2, to_f32(pbase[kl * kstride]) * kLog2e);
                     }
                     s[kb][i] = ok ? x : -INFINITY;
                     mxp[i & 3] = fmaxf(mxp[i & 3], s[kb][i]);
@@ -352,7 +361,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
         return s[0][0];
 #endif
         float mx = fmaxf(fmaxf(mxp[0], mxp[1]), fmaxf(mxp[2], mxp[3]));
-        if constexpr (!kPair) mx *= c2;
+        if constexpr (!kLog2Tile) mx *= c2;
         return half_swap_max(mx);
     };
     auto finish_all = [&](auto masked, f32x16 (&s)[QB][KB], float (&mx)[QB], int t, uint64_t valid) {
@@ -379,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
 #if NNOP_ABL != 2
-                    if constexpr (kPair) s[z][kb][i0 + j] = fast_exp2(s[z][kb][i0 + j] - msub[z]);
+                    if constexpr (kLog2Tile) s[z][kb][i0 + j] = fast_exp2(s[z][kb][i0 + j] - msub[z]);
                     else s[z][kb][i0 + j] = fast_exp2(__builtin_fmaf(s[z][kb][i0 + j], c2, -msub[z]));
 #endif
                     if constexpr (!kMfmaSum) lp[z][j & 3] += s[z][kb][i0 + j];

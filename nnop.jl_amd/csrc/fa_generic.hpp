@@ -48,6 +48,7 @@ NNOP_DEV void generic_key_range(int causal, int wl, int wr, int qi, int KL, int&
 
 #define NNOP_GENERIC_NAME fa_fwd_generic_kernel
 #define NNOP_GENERIC_SINK false
+#define NNOP_GENERIC_CAP false
 #include "fa_fwd_generic_kernel.inc"
 #undef NNOP_GENERIC_NAME
 #undef NNOP_GENERIC_SINK
@@ -56,6 +57,19 @@ NNOP_DEV void generic_key_range(int causal, int wl, int wr, int qi, int KL, int&
 #include "fa_fwd_generic_kernel.inc"
 #undef NNOP_GENERIC_NAME
 #undef NNOP_GENERIC_SINK
+#undef NNOP_GENERIC_CAP
+#define NNOP_GENERIC_CAP true
+#define NNOP_GENERIC_NAME fa_fwd_generic_cap_kernel
+#define NNOP_GENERIC_SINK false
+#include "fa_fwd_generic_kernel.inc"
+#undef NNOP_GENERIC_NAME
+#undef NNOP_GENERIC_SINK
+#define NNOP_GENERIC_NAME fa_fwd_generic_cap_sink_kernel
+#define NNOP_GENERIC_SINK true
+#include "fa_fwd_generic_kernel.inc"
+#undef NNOP_GENERIC_NAME
+#undef NNOP_GENERIC_SINK
+#undef NNOP_GENERIC_CAP
 
 
 // lse = ms + log(ls) (natural units; -inf for a row without a visible key) and delta = sum_e dO * o, per query row
@@ -77,8 +91,9 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_pre_kernel(const BwdParams
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams p, int E, long long n_rows) {
+// (body shared by fa_bwd_generic_dq_kernel and its soft-capped twin fa_bwd_generic_dq_cap_kernel; CAP = false compiles the cap away)
+template <typename T, bool CAP>
+NNOP_DEV void fa_bwd_generic_dq_body(const BwdParams& p, int E, long long n_rows) {
     __shared__ float qs_all[4][kGenericMaxE], dos_all[4][kGenericMaxE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + wave;
@@ -107,13 +122,17 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams 
         const int k = k0 + lane;
         const bool valid = !dead && k < kend && (!mp || mp[k] != 0);
         const int kc = k < p.KL ? k : p.KL - 1;
-        float s = dot_lds(qs, kb + (size_t)kc * E, E) * p.scale;
+        float s = dot_lds(qs, kb + (size_t)kc * E, E);
+        float th = 0.f;                                              // CAP: tanh(s * scale / c)
+        if constexpr (CAP) { th = cap_tanh(s, p.cap_ka); s = th * (p.cap_kb * kLn2); }
+        else s *= p.scale;
         const size_t po = (((size_t)b * p.KL + kc) * p.QL + qi) * p.QH + qh;
         if (p.pair) s += to_f32(((const T*)p.pair)[po]);
         const float pr = valid ? __expf(s - lse) : 0.f;
         const float dp = dot_lds(dos, vb + (size_t)kc * E, E);
-        const float ds = pr * (dp - delta);
+        float ds = pr * (dp - delta);
         if (p.dpair && k < kend) ((T*)p.dpair)[po] = from_f32<T>(ds);      // dpair = dS (src/attention_bwd.jl:123-132); the rest is zero-filled
+        if constexpr (CAP) ds *= __builtin_fmaf(-th, th, 1.f);       // through the tanh: dS' = dS (1 - tanh^2)
         const int nk = kend - k0 < 64 ? kend - k0 : 64;
         for (int kk = 0; kk < nk; ++kk) {
             const float dk_ = lane_bcast(ds, kk);
@@ -133,7 +152,16 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams 
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParams p, int E, long long n_krows) {
+__global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams p, int E, long long n_rows) {
+    fa_bwd_generic_dq_body<T, false>(p, E, n_rows);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void fa_bwd_generic_dq_cap_kernel(const BwdParams p, int E, long long n_rows) {
+    fa_bwd_generic_dq_body<T, true>(p, E, n_rows);
+}
+
+template <typename T, bool CAP>
+NNOP_DEV void fa_bwd_generic_dkdv_body(const BwdParams& p, int E, long long n_krows) {
     __shared__ float ks_all[4][kGenericMaxE], vs_all[4][kGenericMaxE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long krow = (long long)blockIdx.x * 4 + wave;      // over [B][KH][KL]
@@ -168,11 +196,15 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParam
                 const int qc = q < p.QL ? q : p.QL - 1;
                 const float lse = p.nl[rbase + qc];
                 const bool valid = q < qend && q >= qlo && lse > -INFINITY;
-                float s = dot_lds(ks, qb + (size_t)qc * E, E) * p.scale;
+                float s = dot_lds(ks, qb + (size_t)qc * E, E);
+                float th = 0.f;
+                if constexpr (CAP) { th = cap_tanh(s, p.cap_ka); s = th * (p.cap_kb * kLn2); }
+                else s *= p.scale;
                 if (p.pair) s += to_f32(((const T*)p.pair)[(((size_t)b * p.KL + k) * p.QL + qc) * p.QH + qh]);
                 const float pr = valid ? __expf(s - lse) : 0.f;
                 const float dp = dot_lds(vs, dob + (size_t)qc * E, E);
-                const float ds = pr * (dp - p.delta[rbase + qc]);
+                float ds = pr * (dp - p.delta[rbase + qc]);
+                if constexpr (CAP) ds *= __builtin_fmaf(-th, th, 1.f);
                 const int nq = p.QL - q0 < 64 ? p.QL - q0 : 64;
                 for (int qq = 0; qq < nq; ++qq) {
                     const float pq = lane_bcast(pr, qq), dsq = lane_bcast(ds, qq);
@@ -195,6 +227,14 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParam
             ((T*)p.dv)[krow * E + e] = from_f32<T>(dv[j]);
         }
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParams p, int E, long long n_krows) {
+    fa_bwd_generic_dkdv_body<T, false>(p, E, n_krows);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_cap_kernel(const BwdParams p, int E, long long n_krows) {
+    fa_bwd_generic_dkdv_body<T, true>(p, E, n_krows);
 }
 
 }  // namespace nnop

@@ -28,6 +28,7 @@ struct FwdArgs {
     const uint8_t* kpad;
     FaWindow win = {};
     const float* sinks = nullptr;       // learned per-head attention sinks, fp32 [QH] (nnop_fa_fwd_sinks); nullptr = none
+    float softcap = 0;                  // logit soft-capping c (nnop_fa_fwd_softcap): c * tanh(s / c) on the scaled scores; 0 = none
 };
 
 struct BwdArgs {
@@ -39,14 +40,26 @@ struct BwdArgs {
     FaWindow win = {};
     const float* sinks = nullptr;       // nnop_fa_bwd_sinks: the forward's sinks, and their gradient fp32 [QH] (launch_bwd_sinks)
     float* dsinks = nullptr;
+    float softcap = 0;                  // nnop_fa_bwd_softcap: the forward's cap; 0 = none
 };
+
+// The two constants of a capped kernel (fa_common.hpp cap_tanh), folded once on the host: tanh(s * scale / c) = 1 - 2 / (exp2(raw * ka) + 1)
+// for the raw q.k accumulator, and the capped logit in log2 units is kb * tanh.
+struct SoftcapK { float ka = 0, kb = 0; };
+inline SoftcapK softcap_k(double scale, float c) {
+    SoftcapK k;
+    k.ka = (float)(scale / (double)c * 2.0 * 1.4426950408889634);
+    k.kb = (float)((double)c * 1.4426950408889634);
+    return k;
+}
 
 // One per dtype (fa_fwd_{f32,f16,bf16}.hip).  Return an nnop_status.
 template <typename T> int launch_fwd(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s);
 // Which kernel form launch_fwd picks (no launch): 0 = 32-row waves, 1 = split-KV, 2 = 64-row waves, 3 = the plain-HIP kernel of
 // fa_generic.hpp (embedding dims outside the tiled set), 4 = two waves per SIMD in alternating phases (fa_fwd_duo.hpp).
 enum FwdForm { kFormRow32 = 0, kFormSplit = 1, kFormW64 = 2, kFormGeneric = 3, kFormDuo = 4 };
-// A windowed problem (FaWindow::on) always runs kFormRow32 or kFormGeneric.
+// A windowed problem (FaWindow::on) always runs kFormRow32 or kFormGeneric, and so does a capped one (softcap != 0): callers pass
+// `windowed` = window on or cap on.
 int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed = false);
 // Which backward kernels launch_bwd picks (no launch): bit 0: dK/dV on fa_bwd_w64_kernel, bit 1: dQ on it (else fa_bwd.hpp's)
 int bwd_forms(const nnop_fa_desc& d, bool has_pair, bool windowed = false);

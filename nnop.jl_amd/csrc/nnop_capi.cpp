@@ -70,6 +70,8 @@ static int check_opts(const nnop_fa_opts* o) {
     if (o->window_left < -1 || o->window_right < -1) return NNOP_ERR_OPTS;
     return NNOP_OK;
 }
+// logit soft-capping (checked after the options): 0 = none, else finite and positive
+static int check_softcap(float c) { return (c >= 0.f && c <= 3.4028234664e38f) ? NNOP_OK : NNOP_ERR_OPTS; }     // (false for NaN)
 // pair / dpair [B][KL][QL][QH]: inside one kv tile the kernels address the bias with 32-bit element offsets
 // (local key < 64) * QL * QH
 static int check_pair(const nnop_fa_desc* d) {
@@ -116,6 +118,21 @@ int nnop_debug_bwd_form_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, int 
     (void)has_mask;
     return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on());
 }
+int nnop_debug_fwd_form_cap(const nnop_fa_desc* d, const nnop_fa_opts* opts, float softcap, int has_pair, int has_mask) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
+    if (st == NNOP_OK) st = check_softcap(softcap);
+    if (st != NNOP_OK) return st;
+    return fwd_form(*d, has_pair != 0, has_mask != 0, fa_window(*d, opts).on() || softcap != 0.f);
+}
+int nnop_debug_bwd_form_cap(const nnop_fa_desc* d, const nnop_fa_opts* opts, float softcap, int has_pair, int has_mask) {
+    int st = check_desc(d);
+    if (st == NNOP_OK) st = check_opts(opts);
+    if (st == NNOP_OK) st = check_softcap(softcap);
+    if (st != NNOP_OK) return st;
+    (void)has_mask;
+    return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on() || softcap != 0.f);
+}
 int nnop_debug_dev_build(void) {
 #ifdef NNOP_DEV_BUILD
     return 1;
@@ -141,7 +158,7 @@ const char* nnop_strerror(int status) {
         case NNOP_ERR_ALIGN:
             return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls).";
         case NNOP_ERR_OPTS:
-            return "Invalid attention options (a reserved field is not 0, or a window side is below -1).";
+            return "Invalid attention options (a reserved field is not 0, a window side is below -1, or a soft cap is negative or not finite).";
         default: return "unknown nnop status";
     }
 }
@@ -209,8 +226,15 @@ int nnop_fa_fwd_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, void* o, voi
 int nnop_fa_fwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, void* o, void* ms, void* ls,
                       const void* q, const void* k, const void* v, const void* pair, const uint8_t* kpad_mask,
                       nnop_stream_t stream) {
+    return nnop_fa_fwd_softcap(d, opts, sinks, 0.f, o, ms, ls, q, k, v, pair, kpad_mask, stream);
+}
+
+int nnop_fa_fwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float softcap, void* o, void* ms,
+                        void* ls, const void* q, const void* k, const void* v, const void* pair, const uint8_t* kpad_mask,
+                        nnop_stream_t stream) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
+    if (st == NNOP_OK) st = check_softcap(softcap);
     if (st != NNOP_OK) return st;
     if (!o || !ms || !ls || !q || !k || !v) return NNOP_ERR_NULL;
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
@@ -220,7 +244,7 @@ int nnop_fa_fwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const flo
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(sinks, sizeof(float)))
             return NNOP_ERR_ALIGN;
     }
-    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts), sinks};
+    FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts), sinks, softcap};
     hipStream_t s = (hipStream_t)stream;
     switch (d->dtype) {
         case NNOP_F32:  return launch_fwd<float>(*d, a, s);
@@ -338,8 +362,17 @@ int nnop_fa_bwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const flo
                       void* dv, void* dpair, const void* d_o, const void* o, const void* ms, const void* ls, const void* q,
                       const void* k, const void* v, const void* pair, const uint8_t* kpad_mask, void* workspace,
                       size_t workspace_bytes, nnop_stream_t stream) {
+    return nnop_fa_bwd_softcap(d, opts, sinks, dsinks, 0.f, dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace,
+                               workspace_bytes, stream);
+}
+
+int nnop_fa_bwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const float* sinks, float* dsinks, float softcap, void* dq,
+                        void* dk, void* dv, void* dpair, const void* d_o, const void* o, const void* ms, const void* ls,
+                        const void* q, const void* k, const void* v, const void* pair, const uint8_t* kpad_mask, void* workspace,
+                        size_t workspace_bytes, nnop_stream_t stream) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
+    if (st == NNOP_OK) st = check_softcap(softcap);
     if (st != NNOP_OK) return st;
     if (!sinks) dsinks = nullptr;                          // ignored without sinks, as dpair is without pair
     if (!dq || !dk || !dv || !d_o || !o || !ms || !ls || !q || !k || !v || !workspace) return NNOP_ERR_NULL;
@@ -356,7 +389,7 @@ int nnop_fa_bwd_sinks(const nnop_fa_desc* d, const nnop_fa_opts* opts, const flo
             return NNOP_ERR_ALIGN;
     }
     BwdArgs a{dq, dk, dv, dpair, d_o, o, ms, ls, q, k, v, pair, kpad_mask, workspace, workspace_bytes, fa_window(*d, opts),
-              sinks, dsinks};
+              sinks, dsinks, softcap};
     hipStream_t s = (hipStream_t)stream;
     // dQ, dK, dV (and dpair) need nothing for a sink: they recompute P from (ms, ls), which include it.  dsinks: one more pass behind them
     switch (d->dtype) {

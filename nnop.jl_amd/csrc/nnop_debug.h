@@ -33,6 +33,11 @@ struct nnop_fa_opts;
 int nnop_debug_fwd_form_ex(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, int has_pair, int has_mask);
 int nnop_debug_bwd_form_ex(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, int has_pair, int has_mask);
 
+/* The same two rules for a call with logit soft-capping (nnop_fa_fwd_softcap): a cap > 0 always reports 0 / 3 forward and no w64
+ * backward bits; softcap == 0 reports what the _ex hooks report.  NNOP_ERR_OPTS for a negative or non-finite cap. */
+int nnop_debug_fwd_form_cap(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, float softcap, int has_pair, int has_mask);
+int nnop_debug_bwd_form_cap(const struct nnop_fa_desc* d, const struct nnop_fa_opts* opts, float softcap, int has_pair, int has_mask);
+
 /* 1 when the library was built with `make DEV=1` (timing ablations, experimental kernel bodies compiled in). */
 int nnop_debug_dev_build(void);
 

@@ -32,7 +32,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention, flash_attention_sinks
+export local_flash_attention, flash_attention_sinks, softcap_flash_attention
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -309,6 +309,91 @@ function NNop.CRC.rrule(::typeof(flash_attention_sinks), q, k, v, sinks, pair = 
         return NNop.CRC.NoTangent(), dq, dk, dv, ds, isnothing(pair) ? NNop.CRC.NoTangent() : dp
     end
     return o, flash_attention_sinks_pullback
+end
+
+# ---- logit soft-capping (include/nnop_hip.h: nnop_fa_fwd_softcap / nnop_fa_bwd_softcap) ---------------------------------------------
+# The scaled scores become softcap * tanh(scale * q.k / softcap) (Gemma-2: 50, Grok-1: 30) before the pair bias is added and the masks
+# and the softmax apply; the bias and the sinks are not capped.  fp32 arithmetic for every element type.  `window = nothing`: no options
+# (a NULL nnop_fa_opts); `sinks = nothing`: no sinks (NULL); `softcap = 0`: no cap -- the library then runs exactly the sinks call.
+_opts_ref(window::Nothing) = nothing
+_opts_ref(window::Tuple{Integer, Integer}) = Ref(FaOpts(window))
+_opts_ptr(op::Nothing) = Ptr{FaOpts}(C_NULL)
+_opts_ptr(op::Ref{FaOpts}) = Base.unsafe_convert(Ptr{FaOpts}, op)
+
+function softcap_flash_attention_fwd(
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing, window::Union{Nothing,Tuple{Integer, Integer}} = nothing,
+    sinks::Union{Nothing,ROCVector{Float32}} = nothing, softcap::Real,
+) where T <: HipFloat
+    check_abi()
+    isnothing(sinks) || length(sinks) == size(q, 3) ||
+        error("sinks must have one entry per query head ($(size(q, 3))), got $(length(sinks))")
+    d = Ref(desc(q, k, v, causal))
+    op = _opts_ref(window)
+    o  = similar(q)
+    ms = ROCArray{T}(undef, size(q, 2), size(q, 3), size(q, 4))
+    ls = similar(ms)
+    st = GC.@preserve op o ms ls q k v sinks pair kpad_mask ccall((:nnop_fa_fwd_softcap, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Cfloat,                        # sinks softcap
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, _opts_ptr(op), devptr(sinks), Cfloat(softcap), devptr(o), devptr(ms), devptr(ls), devptr(q), devptr(k), devptr(v),
+        devptr(pair), devptr(kpad_mask), hipstream())
+    check(st, q, k, v)
+    return o, ms, ls
+end
+
+function softcap_flash_attention_bwd(
+    Δ::ROCArray{T,4}, o::ROCArray{T,4}, ms::ROCArray{T,3}, ls::ROCArray{T,3},
+    q::ROCArray{T,4}, k::ROCArray{T,4}, v::ROCArray{T,4}, pair::Union{Nothing,ROCArray{T,4}} = nothing;
+    causal::Bool, kpad_mask::Union{Nothing,ROCMatrix{Bool}} = nothing, window::Union{Nothing,Tuple{Integer, Integer}} = nothing,
+    sinks::Union{Nothing,ROCVector{Float32}} = nothing, softcap::Real,
+) where T <: HipFloat
+    d = Ref(desc(q, k, v, causal))
+    op = _opts_ref(window)
+    # a cap needs no more scratch than the plain backward (with a pair bias it always takes the direct path)
+    nbytes = ccall((:nnop_fa_bwd_workspace_bytes, libnnop()), Csize_t, (Ptr{FaDesc},), d)
+    nbytes == 0 && error("libnnop_hip: invalid attention descriptor")
+    dq, dk, dv = similar(q), similar(k), similar(v)
+    dp = isnothing(pair) ? nothing : similar(pair)
+    ds = isnothing(sinks) ? nothing : similar(sinks)
+    ws = ROCArray{UInt8}(undef, nbytes)
+    st = GC.@preserve op dq dk dv dp ds Δ o ms ls q k v sinks pair kpad_mask ws ccall((:nnop_fa_bwd_softcap, libnnop()), Cint,
+        (Ptr{FaDesc}, Ptr{FaOpts}, Ptr{Cvoid}, Ptr{Cvoid}, Cfloat,            # sinks dsinks softcap
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},                      # dq dk dv dpair
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},                      # Δ o ms ls
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},          # q k v pair kpad_mask
+         Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),                                    # workspace, bytes, stream
+        d, _opts_ptr(op), devptr(sinks), devptr(ds), Cfloat(softcap), devptr(dq), devptr(dk), devptr(dv), devptr(dp), devptr(Δ),
+        devptr(o), devptr(ms), devptr(ls), devptr(q), devptr(k), devptr(v), devptr(pair), devptr(kpad_mask), devptr(ws), nbytes,
+        hipstream())
+    check(st, q, k, v)
+    return dq, dk, dv, dp, ds
+end
+
+"""
+    softcap_flash_attention(q, k, v, pair=nothing; causal, kpad_mask=nothing, window=nothing, sinks=nothing, softcap)
+
+Flash Attention with logit soft-capping on the HIP kernels: the scaled scores become `softcap * tanh(scale * q.k / softcap)` before the
+pair bias, the masks and the softmax (Gemma-2: 50, Grok-1: 30).  `window` as for `local_flash_attention`, `sinks` as for
+`flash_attention_sinks`; neither the bias nor the sinks are capped.  Differentiable w.r.t. q, k, v and pair through the ChainRules
+rule below.  NOT w.r.t. `sinks`: they are a keyword here, and ChainRules gives keyword arguments no tangent, so automatic
+differentiation treats them as constants.  To train sinks under a cap call `softcap_flash_attention_fwd` and
+`softcap_flash_attention_bwd` yourself: the fifth value the latter returns is `dsinks`.
+"""
+softcap_flash_attention(q, k, v, pair = nothing; causal::Bool, kpad_mask = nothing, window = nothing, sinks = nothing, softcap::Real) =
+    softcap_flash_attention_fwd(q, k, v, pair; causal, kpad_mask, window, sinks, softcap)[1]
+
+# the shape of local_flash_attention's rule: no tangent for the cap, the window or the mask.  ChainRules gives keyword arguments no
+# tangent, so `sinks` gets none here: softcap_flash_attention_bwd returns their gradient for a caller that trains them under a cap
+function NNop.CRC.rrule(::typeof(softcap_flash_attention), q, k, v, pair = nothing;
+                                   causal::Bool, kpad_mask = nothing, window = nothing, sinks = nothing, softcap::Real)
+    o, ms, ls = softcap_flash_attention_fwd(q, k, v, pair; causal, kpad_mask, window, sinks, softcap)
+    function softcap_flash_attention_pullback(Δ)
+        dq, dk, dv, dp, _ = softcap_flash_attention_bwd(_to_roc(NNop.CRC.unthunk(Δ), o), o, ms, ls, q, k, v, pair;
+                                                        causal, kpad_mask, window, sinks, softcap)
+        return NNop.CRC.NoTangent(), dq, dk, dv, isnothing(pair) ? NNop.CRC.NoTangent() : dp
+    end
+    return o, softcap_flash_attention_pullback
 end
 
 # ---- several devices (include/nnop_hip.h: nnop_fa_shards, ABI version 6) -------------------------------------------------------------

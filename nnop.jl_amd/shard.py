@@ -118,8 +118,8 @@ def forward_with_overlapped_gather(step_chunk, o_chunks, full_chunks, group=None
 def flash_attention_sharded(q, k, v, pair=None, *, causal: bool, kpad_mask=None,
                             world: Optional[int] = None, rank: Optional[int] = None,
                             gather: bool = False, group=None,
-                            attn_fn: Optional[Callable] = None, window=None):
-    """Run this rank's share of ``flash_attention(q,k,v,pair; causal,kpad_mask,window)``.
+                            attn_fn: Optional[Callable] = None, window=None, softcap=None):
+    """Run this rank's share of ``flash_attention(q,k,v,pair; causal,kpad_mask,window,softcap)``.
 
     Inputs are the FULL (replicated) tensors; the rank computes only its (batch, kv-head)
     rectangles.  Returns the local output as ``[units_local * rep, QL, E]``-shaped rows in unit
@@ -138,10 +138,12 @@ def flash_attention_sharded(q, k, v, pair=None, *, causal: bool, kpad_mask=None,
     outs = []
     for rect in rectangles(B, KH, world, rank):
         qs, ks, vs, ps, ms = shard_views(rect, q, k, v, pair, kpad_mask)
-        if window is None:
-            o = attn_fn(qs, ks, vs, ps, causal=causal, kpad_mask=ms)
-        else:
-            o = attn_fn(qs, ks, vs, ps, causal=causal, kpad_mask=ms, window=window)
+        extra = {}                              # (a stand-in attn_fn sees only the options that are in use)
+        if window is not None:
+            extra["window"] = window
+        if softcap is not None:
+            extra["softcap"] = softcap
+        o = attn_fn(qs, ks, vs, ps, causal=causal, kpad_mask=ms, **extra)
         outs.append(o.reshape(rect.units, rep, QL, E))
     if outs:
         local = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
@@ -154,7 +156,7 @@ def flash_attention_sharded(q, k, v, pair=None, *, causal: bool, kpad_mask=None,
 
 
 def flash_attention_sharded_fwd_bwd(q, k, v, dO, pair=None, *, causal: bool, kpad_mask=None,
-                                    world: int, rank: int, window=None):
+                                    world: int, rank: int, window=None, softcap=None):
     """This rank's share of one forward + backward, without autograd: for each of the rank's rectangles
     ``_flash_attention`` then ``grad_flash_attention`` on the rectangle's views (pointer offsets only).
 
@@ -169,7 +171,8 @@ def flash_attention_sharded_fwd_bwd(q, k, v, dO, pair=None, *, causal: bool, kpa
     for rect in rectangles(q.shape[0], k.shape[1], world, rank):
         qs, ks, vs, ps, ms_ = shard_views(rect, q, k, v, pair, kpad_mask)
         dos = dO[rect.b0:rect.b1, rect.kh0 * rep:rect.kh1 * rep]
-        o, m, l = _flash_attention(qs, ks, vs, ps, causal=causal, kpad_mask=ms_, window=window)
-        dq, dk, dv, dp = grad_flash_attention(dos, o, m, l, qs, ks, vs, ps, causal=causal, kpad_mask=ms_, window=window)
+        o, m, l = _flash_attention(qs, ks, vs, ps, causal=causal, kpad_mask=ms_, window=window, softcap=softcap)
+        dq, dk, dv, dp = grad_flash_attention(dos, o, m, l, qs, ks, vs, ps, causal=causal, kpad_mask=ms_, window=window,
+                                              softcap=softcap)
         out.append((rect, o, dq, dk, dv, dp))
     return out
