@@ -90,25 +90,16 @@ static int launch_bwd_w64(const nnop_fa_desc& d, const BwdParams& p, hipStream_t
     if (n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     pk.n_wg = (int)n_wg;
     if (n_wg * SH::NSPLIT > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    // Persistent form (as the forward's, fa_fwd_inst.hpp launch_fwd_w64): 256 workgroups over a static balanced block list, under a
-    // causal mask without key padding, when the list divides.  Knob kTuneBwdPersist (0 never, 1 wherever it divides).
+    // Persistent form (persist_list, fa_launch.hpp), under a causal mask without key padding.  Knob kTuneBwdPersist.
     long long grid = n_wg * SH::NSPLIT;
-    pk.persist = 0;
     if constexpr (MODE == 1 && SH::NSPLIT == 1) {
-        const long long cols = (long long)d.batch * hd;
-        const int n = pk.n_blk;
-        const long long per_xcd = (cols / 8) * n;
-        const int knob = tune_get(kTuneBwdPersist);
-        const int hx = hd % 8 == 0 ? hd / 8 : 0;
         // (key padding without a causal mask: the dQ pass only -- every query block of a batch costs the same there, while the key
         // blocks of the dK/dV pass are full or EMPTY by the batch's length and a static list cannot pair them up: measured -17 % at C4)
-        const bool pays = (d.causal && !p.kpad) || (KIND == kBwdDQ && !d.causal && p.kpad && hx > 0);
-        if ((knob == 1 || (knob < 0 && pays)) && device_cu_count() == 256 && cols % 8 == 0 && (n & (n - 1)) == 0 &&
-            per_xcd % 32 == 0 && per_xcd / 32 >= 2 && per_xcd / 32 <= (1 << 24)) {
-            pk.persist = (int)(per_xcd / 32);
-            pk.persist_hx = hx;
-            grid = 256;
-        }
+        const bool pays = (d.causal && !p.kpad) || (KIND == kBwdDQ && !d.causal && p.kpad && hd % 8 == 0);
+        const PersistList l = persist_list((long long)d.batch * hd, hd, pk.n_blk, tune_get(kTuneBwdPersist), pays);
+        pk.persist = l.steps;
+        pk.persist_hx = l.hx;
+        if (l.steps > 0) grid = 256;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, pk);      // E = 256 dK/dV: every block twice (column halves)
     return NNOP_OK;
@@ -137,37 +128,41 @@ static inline bool bwd_w64_narrow(const nnop_fa_desc& d, int kind) {
     return small_grid_prefers_32_row_waves(len, (long long)hd * d.batch, d.causal != 0);
 }
 // bit 0: dK/dV runs fa_bwd_w64_kernel, bit 1: dQ does (knob kTuneBwdW64: 0 never, 1 both, 2 dK/dV only, 3 dQ only, 4 both with the
-// preprocess launch kept, auto = both).  Never with a sliding window (fa_bwd.hpp WIN only) or a soft cap (`windowed` covers both).
-static inline int bwd_w64_forms(const nnop_fa_desc& d, bool has_pair, bool ws_aligned16, bool windowed = false) {
-    if (has_pair || windowed) return 0;
+// preprocess launch kept, auto = both).  Never with a sliding window or a soft cap (the WIN / kBwdCap bodies of fa_bwd.hpp only).
+static inline int bwd_w64_forms(const nnop_fa_desc& d, bool has_pair, bool ws_aligned16, bool win_on, bool capped) {
+    if (has_pair || win_on || capped) return 0;
     const int t = tune_get(kTuneBwdW64);
     const bool want_kv = t < 0 || t == 1 || t == 2 || t == 4, want_q = t < 0 || t == 1 || t == 3 || t == 4;
     return ((want_kv && ws_aligned16 && bwd_w64_ok(d, kBwdDKDV)) ? 1 : 0) | ((want_q && bwd_w64_ok(d, kBwdDQ)) ? 2 : 0);
+}
+
+// Everything in BwdParams that is a plain function of (descriptor, arguments); the rest is zero / null / unbounded.  The layout of the
+// row constants in the workspace (QLs, delta, rcf) and the pair scratch are the launcher's own.
+static inline void bwd_params(BwdParams& p, const nnop_fa_desc& d, const BwdArgs& a) {
+    p = BwdParams{};
+    p.dq = a.dq; p.dk = a.dk; p.dv = a.dv; p.dpair = a.pair ? a.dpair : nullptr;
+    p.d_o = a.d_o; p.o = a.o; p.ms = a.ms; p.ls = a.ls;
+    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    p.nl = (float*)a.workspace;
+    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
+    p.causal = d.causal ? 1 : 0;
+    p.scale = (float)(1.0 / sqrt((double)d.emb));
+    p.win_left = a.win.left; p.win_right = a.win.right;
+    if (a.softcap != 0.f) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
 }
 
 template <typename T, int E, int MODE, bool WIN = false>
 static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) {
     using C = BwdCfg<T, E>;
     BwdParams p;
-    p.dq = a.dq; p.dk = a.dk; p.dv = a.dv; p.dpair = a.pair ? a.dpair : nullptr;
-    p.d_o = a.d_o; p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    bwd_params(p, d, a);
     p.QLs = (d.ql + 63) & ~63;
     const long long n_rows = (long long)d.batch * d.qh * p.QLs;            // padded rows (bwd_workspace_bytes)
     if (n_rows > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    p.nl = (float*)a.workspace;
     p.delta = p.nl + n_rows;
     // the fragment form of the row constants (fa_bwd_w64.hpp, dK/dV): behind the two vectors (n_rows is a multiple of 64: the offset
     // keeps the workspace's alignment); 16-byte stores / LDS-DMA -> only with a 16-byte aligned workspace
     p.rcf = (bwd_has_rcf(d) && ((uintptr_t)a.workspace & 15) == 0) ? (void*)(p.delta + n_rows) : nullptr;
-    p.fused = 0;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
-    if constexpr ((MODE & kBwdCap) != 0) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)E), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
-    p.scale = (float)(1.0 / sqrt((double)E));
-    p.n_blk = 0; p.n_wg = 0;
-    p.pair_a = nullptr; p.dpair_s = nullptr;
     p.QLp = pair_pad(d.ql); p.KLp = pair_pad(d.kl);
     if constexpr (MODE == 3) {
         // scratch behind the two row vectors: the head-major copy of the bias, dS (bwd_workspace_bytes_pair)
@@ -184,7 +179,7 @@ static int launch_bwd_cfg(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s
     // measurement only (kTuneBwdStages, bench.py's per-kernel times): run a subset of the passes -- 1 preprocess, 2 dK/dV, 4 dQ
     const int stages = tune_get(kTuneBwdStages) < 0 ? 7 : tune_get(kTuneBwdStages);
     // the one-wave-per-SIMD form (fa_bwd_w64.hpp): 16-bit, E = 64 / 128, plain / masked modes
-    const int w64_forms = (MODE <= 1 && !WIN) ? bwd_w64_forms(d, false, p.rcf != nullptr) : 0;
+    const int w64_forms = bwd_w64_forms(d, a.pair != nullptr, p.rcf != nullptr, a.win.on(), a.softcap != 0.f);
     const bool w64_kv = (w64_forms & 1) != 0, w64_q = (w64_forms & 2) != 0;
     // Both passes in that form: no preprocess launch -- the dQ kernel computes the row constants of its own rows and leaves them
     // (fragment form) for the dK/dV kernel, which therefore runs BEHIND it.  (kTuneBwdW64 = 4: both passes, preprocess kept: A/B)
@@ -323,22 +318,10 @@ static int launch_bwd_e(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) 
 
 template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s) {
     BwdParams p;
-    p.dq = a.dq; p.dk = a.dk; p.dv = a.dv; p.dpair = a.pair ? a.dpair : nullptr;
-    p.d_o = a.d_o; p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    bwd_params(p, d, a);
     const long long n_rows = (long long)d.batch * d.qh * d.ql, n_krows = (long long)d.batch * d.kh * d.kl;
-    p.QLs = d.ql;                                                          // dense rows here
-    p.rcf = nullptr; p.fused = 0;
-    p.nl = (float*)a.workspace;
+    p.QLs = d.ql;                                                          // dense rows here, no pair scratch (QLp = KLp = 0)
     p.delta = p.nl + n_rows;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    p.win_left = a.win.left; p.win_right = a.win.right;
-    p.scale = (float)(1.0 / sqrt((double)d.emb));
-    const bool capped = a.softcap != 0.f;
-    if (capped) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
-    p.n_blk = 0; p.n_wg = 0;
-    p.pair_a = nullptr; p.dpair_s = nullptr; p.QLp = p.KLp = 0;
     const long long gq = (n_rows + 3) / 4, gk = (n_krows + 3) / 4;
     if (gq > 0x7fffffffLL || gk > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     if (p.dpair) {      // the dQ kernel writes dS only where a query sees the key
@@ -346,7 +329,7 @@ template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const
         if (hipMemsetAsync(p.dpair, 0, bytes, s) != hipSuccess) { (void)hipGetLastError(); return NNOP_ERR_HIP; }
     }
     hipLaunchKernelGGL((fa_bwd_generic_pre_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-    if (capped) {
+    if (a.softcap != 0.f) {
         hipLaunchKernelGGL((fa_bwd_generic_dq_cap_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
         hipLaunchKernelGGL((fa_bwd_generic_dkdv_cap_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
     } else {

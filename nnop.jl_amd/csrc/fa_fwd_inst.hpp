@@ -26,6 +26,29 @@ static inline int dev_env_int(const char* name, int dflt) {
 }
 #endif
 
+// Everything in FwdParams that is a plain function of (descriptor, arguments, query rows per workgroup); the rest is zero / unbounded.
+// A launcher then sets only what is its own (causal_alt, the persist fields, stagger).  rows = 0: the plain-HIP kernel, whose grid is
+// not one of row blocks.  (The split, w64 and duo kernels never read pair, and the split kernel neither kpad nor causal: those forms
+// are chosen only for calls that have none -- fwd_form_of: mode != 2, mode == 0 -- so the arguments pass through as they are.)
+static inline int fwd_params(FwdParams& p, const nnop_fa_desc& d, const FwdArgs& a, int rows) {
+    p = FwdParams{};
+    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
+    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
+    p.sinks = a.sinks;
+    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
+    p.causal = d.causal ? 1 : 0;
+    p.scale = (float)(1.0 / sqrt((double)d.emb));    // T(inv(sqrt(QE))), src/attention.jl:154
+    p.win_left = a.win.left; p.win_right = a.win.right;
+    if (a.softcap != 0.f) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
+    if (rows > 0) {
+        p.n_qblk = (d.ql + rows - 1) / rows;
+        const long long n_wg = (long long)p.n_qblk * d.qh * d.batch;
+        if (n_wg <= 0 || n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
+        p.n_wg = (int)n_wg;
+    }
+    return NNOP_OK;
+}
+
 template <typename T, int E, int NW, int MODE, int QB, bool WIN = false, bool CAP = false>
 static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     // 64-key tiles, except the E = 128 pair-bias body (register budget) and fp32 E = 128
@@ -41,26 +64,14 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     static unsigned long long lds_done[2] = {0, 0};
     if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
-    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
-    p.sinks = a.sinks;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    constexpr int rows = 32 * QB * NW;
-    p.n_qblk = (d.ql + rows - 1) / rows;
-    const long long n_wg = (long long)p.n_qblk * d.qh * d.batch;
-    if (n_wg <= 0 || n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    p.n_wg = (int)n_wg;
-    p.scale = (float)(1.0 / sqrt((double)E));        // T(inv(sqrt(QE))), src/attention.jl:154
+    if (const int st = fwd_params(p, d, a, 32 * QB * NW); st != NNOP_OK) return st;
     // Causal launches of a few rounds: pair heavy with light blocks on a CU (fa_launch.hpp causal_alt_run).  Measured (round 4,
     // profiles/r04/causal_alt.log): fp32 E64 L4096 H4 B4 545.6 -> 319.6 us, fp32 E32 301 -> 180, fp32 E16 233 -> 142, bf16 E16 69.8 -> 53.0,
     // fp32 E64 L2048 H8 B8 (4 rounds) 473 -> 428; GQA at 4 rounds -5 %, 8 rounds and more -12 % (the rule stops before).  Where ONE workgroup
     // fills a CU there is nothing to pair (E = 128 with 8 waves; fp32 E = 128 with 4 waves fits two).
     // (a window: every block walks about the same number of tiles -- nothing to pair)
     p.causal_alt = (!WIN && MODE != 2 && (E <= 64 || (E == 128 && sizeof(T) == 4 && NW == 4)))
-                       ? causal_alt_run(d.causal != 0, n_wg, (long long)d.qh * d.batch, d.qh / d.kh, p.n_qblk) : 0;
-    if constexpr (WIN) { p.win_left = a.win.left; p.win_right = a.win.right; }
-    if constexpr (CAP) { const SoftcapK ck = softcap_k(1.0 / sqrt((double)E), a.softcap); p.cap_ka = ck.ka; p.cap_kb = ck.kb; }
+                       ? causal_alt_run(d.causal != 0, p.n_wg, (long long)d.qh * d.batch, d.qh / d.kh, p.n_qblk) : 0;
     int lds_launch = lds;
 #ifdef NNOP_DEV_BUILD
     // experiments (make DEV=1 only): de-phase co-resident workgroups; pad LDS to limit workgroups per CU
@@ -72,7 +83,7 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
         return NNOP_ERR_HIP;
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(NW * 64), lds_launch, s, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.n_wg), dim3(NW * 64), lds_launch, s, p);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
@@ -87,49 +98,29 @@ static int launch_fwd_split(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t
     static unsigned long long lds_done[2] = {0, 0};
     if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
-    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = nullptr;
-    p.sinks = a.sinks;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = 0;
-    p.n_qblk = (d.ql + 255) / 256;
-    const long long n_wg = (long long)p.n_qblk * d.qh * d.batch;
-    if (n_wg <= 0 || n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    p.n_wg = (int)n_wg;
-    p.scale = (float)(1.0 / sqrt((double)E));
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(1024), lds, s, p);
+    if (const int st = fwd_params(p, d, a, 256); st != NNOP_OK) return st;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.n_wg), dim3(1024), lds, s, p);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
-// Persistent form of the masked-mode kernels (fa_fwd_w64.hpp, fa_fwd_duo.hpp): 256 workgroups that each walk `persist` blocks of a
-// static, balanced list instead of one workgroup per block -- on a 256-CU device, when the list divides: (batch x q-head) columns in
-// eighths (one per XCD), a power-of-two number of q-blocks per column, whole steps of 32 blocks per XCD, and more than one step.
-// Fills p.persist / p.persist_hx and the grid when the form applies.
+// Persistent form of the masked-mode kernels (fa_fwd_w64.hpp, fa_fwd_duo.hpp): the rule is persist_list (fa_launch.hpp).  Fills
+// p.persist / p.persist_hx / p.persist_asc and the grid when the form applies.
 static inline void fwd_persist_plan(const nnop_fa_desc& d, const FwdArgs& a, FwdParams& p, long long& grid) {
-    const long long bh = (long long)d.batch * d.qh;
-    const int n = p.n_qblk;
-    const long long per_xcd = (bh / 8) * n;
     // (auto: under a causal mask without key padding -- there the static list balances exactly and measured +3..4 % at E = 128
     // L 8192-16384, +23 % at E = 64 L4096 H16 B4; equal-work blocks gain nothing (+-0.3 %), and per-batch key lengths make a
     // static list 15 % SLOWER than the dispatcher's dynamic order: C4)
-    const int knob = tune_get(kTuneFwdPersist);
     // per-batch key lengths WITHOUT a causal mask: balanced as well once every XCD takes an eighth of the heads of every batch
-    const int hx = d.qh % 8 == 0 ? d.qh / 8 : 0;
-    const bool pays = (d.causal && !a.kpad) || (!d.causal && a.kpad && hx > 0);
-    if ((knob == 1 || (knob < 0 && pays)) && device_cu_count() == 256 && bh % 8 == 0 && (n & (n - 1)) == 0 &&
-        per_xcd % 32 == 0 && per_xcd / 32 >= 2 && per_xcd / 32 <= (1 << 24)) {
-        p.persist = (int)(per_xcd / 32);
-        p.persist_hx = hx;
-        // Order of a column's q-blocks: descending (heaviest first).  The ascending order (light blocks first, so that every
-        // workgroup starts at kv tile 0 together and the heavy blocks follow staggered inside each other's L2 window) was built and
-        // measured in round 4: same time (+-0.1 %: C3 3912 vs 3918 us, C5 shard 15084 vs 15100 us), MORE fabric traffic at the C5
-        // shard (7.93 vs 6.11 GB per launch; C3 2.34 vs 2.32 GB) -- profiles/r04/persist_order.log.  Knob kTuneFwdPersistAsc (1 = ascending).
-        {
-            const int asc = tune_get(kTuneFwdPersistAsc);
-            p.persist_asc = asc >= 0 ? (asc != 0) : 0;
-        }
-        grid = 256;
-    }
+    const bool pays = (d.causal && !a.kpad) || (!d.causal && a.kpad && d.qh % 8 == 0);
+    const PersistList l = persist_list((long long)d.batch * d.qh, d.qh, p.n_qblk, tune_get(kTuneFwdPersist), pays);
+    if (l.steps == 0) return;
+    p.persist = l.steps;
+    p.persist_hx = l.hx;
+    // Order of a column's q-blocks: descending (heaviest first).  The ascending order (light blocks first, so that every
+    // workgroup starts at kv tile 0 together and the heavy blocks follow staggered inside each other's L2 window) was built and
+    // measured in round 4: same time (+-0.1 %: C3 3912 vs 3918 us, C5 shard 15084 vs 15100 us), MORE fabric traffic at the C5
+    // shard (7.93 vs 6.11 GB per launch; C3 2.34 vs 2.32 GB) -- profiles/r04/persist_order.log.  Knob kTuneFwdPersistAsc (1 = ascending).
+    p.persist_asc = tune_get(kTuneFwdPersistAsc) > 0 ? 1 : 0;
+    grid = 256;
 }
 
 // 64-rows-per-wave form (fa_fwd_w64.hpp): 4 waves x 64 rows, 16-bit types, E = 64 / 128, plain and masked modes
@@ -142,18 +133,9 @@ static int launch_fwd_w64(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     static unsigned long long lds_done[2] = {0, 0};
     if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
-    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = a.kpad;
-    p.sinks = a.sinks;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    p.n_qblk = (d.ql + 255) / 256;
-    const long long n_wg = (long long)p.n_qblk * d.qh * d.batch;
-    if (n_wg <= 0 || n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    p.n_wg = (int)n_wg;
-    p.scale = (float)(1.0 / sqrt((double)E));
-    if (n_wg * (E / EV) > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    long long grid = n_wg * (E / EV);
+    if (const int st = fwd_params(p, d, a, 256); st != NNOP_OK) return st;
+    long long grid = (long long)p.n_wg * (E / EV);
+    if (grid > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     if constexpr (EV == E && MODE == 1) fwd_persist_plan(d, a, p, grid);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, p);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
@@ -169,33 +151,25 @@ static int launch_fwd_duo(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
     static unsigned long long lds_done[2] = {0, 0};
     if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
-    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = nullptr; p.kpad = a.kpad;
-    p.sinks = a.sinks;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    p.n_qblk = (d.ql + 128 * NZ - 1) / (128 * NZ);
-    const long long n_wg = (long long)p.n_qblk * d.qh * d.batch;
-    if (n_wg <= 0 || n_wg > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    p.n_wg = (int)n_wg;
-    p.scale = (float)(1.0 / sqrt((double)E));
-    long long grid = n_wg;
+    if (const int st = fwd_params(p, d, a, 128 * NZ); st != NNOP_OK) return st;
+    long long grid = p.n_wg;
     if constexpr (MODE == 1) fwd_persist_plan(d, a, p, grid);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, p);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
-template <typename T, int E, int NW, int QB>
-static int launch_fwd_mode(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s, int mode) {
-    if (mode == 0) return launch_fwd_cfg<T, E, NW, 0, QB>(d, a, s);
-    if (mode == 1) return launch_fwd_cfg<T, E, NW, 1, QB>(d, a, s);
-    return launch_fwd_cfg<T, E, NW, 2, QB>(d, a, s);
-}
-
 // The launcher's choice of kernel form, as a plain function of the descriptor (also reported through nnop_debug_fwd_form).
 //   mode: 0 plain (every logit live), 1 masked (causal / key padding / ragged KL / sliding window), 2 + pair bias
-static inline int fwd_mode(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed = false) {
-    return has_pair ? 2 : ((d.causal || has_mask || windowed || (d.kl % 64) != 0) ? 1 : 0);
+//   (a soft cap runs the masked bodies as well: fa_fwd.hpp CAP)
+static inline int fwd_mode(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool win_on, bool capped) {
+    return has_pair ? 2 : ((d.causal || has_mask || win_on || capped || (d.kl % 64) != 0) ? 1 : 0);
+}
+// Workgroups of a forward grid with `rows` query rows each
+static inline long long fwd_wg(const nnop_fa_desc& d, int rows) { return (long long)((d.ql + rows - 1) / rows) * d.qh * d.batch; }
+// Can the one-wave / two-wave forms (fa_fwd_w64.hpp, fa_fwd_duo.hpp) address this problem?  No pair bias; masked mode keeps the per-tile
+// validity words in LDS (KL <= 64 Ki); their LDS-DMA addresses a (batch, kv-head) tensor through a 32-bit buffer offset.
+static inline bool fwd_wide_fits(const nnop_fa_desc& d, int mode) {
+    return mode != 2 && (mode == 0 || d.kl <= 64 * kMaxMaskTiles) && (long long)d.kl * d.emb * 2 < (1LL << 32);
 }
 // Rows per wave of the two-waves-per-SIMD form at E = 64: 64 (NZ = 2, 256-row workgroups), or 32 (NZ = 1: twice the workgroups) where the
 // 256-row blocks leave CUs idle (small_grid_prefers_32_row_waves, fa_launch.hpp; L1024 H8 B4: 19.8 -> 14.0 us; L2048 H4 B4: 30.9 -> 21.4 us;
@@ -206,20 +180,20 @@ static inline int fwd_duo_nz(const nnop_fa_desc& d) {
     if (duo == 3) return 1;
     return small_grid_prefers_32_row_waves(d.ql, (long long)d.qh * d.batch, d.causal != 0) ? 1 : 2;
 }
-static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = false) {
+// wg256 / wg128: fwd_wg of 256- and 128-row workgroups
+static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool win_on, bool capped, long long wg256, long long wg128) {
     const bool b16 = d.dtype != NNOP_F32;
     const int E = d.emb;
     // the early exits of launch_fwd: embedding dims outside the tiled set (16-bit E = 256 runs the 32-row tiled kernel)
     if (E != 256 && emb_generic(E)) return kFormGeneric;
     // a sliding window (FaWindow::on) exists in the 32-row kernel only (fa_fwd.hpp WIN), not in the duo / w64 / split forms; so does a
-    // soft cap (CAP), which callers report as `windowed`
-    if (windowed) return kFormRow32;
-    const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
+    // soft cap (CAP)
+    if (win_on || capped) return kFormRow32;
+    const bool fits = fwd_wide_fits(d, mode);
     if (b16 && E == 256) {
         // E = 256: the 64-row form with two 128-column halves of O per block (spill-free; the 32-row form spills 62-152 registers
         // and measured 214 TFLOP/s at L2048 H8 B2).  No pair bias; masked mode up to 64 Ki keys; a few kv tiles.
         const int w64 = tune_get(kTuneFwdW64);
-        const bool fits = mode != 2 && (mode == 0 || d.kl <= 64 * kMaxMaskTiles) && (long long)d.kl * E * 2 < (1LL << 32);
         if (fits && w64 != 0 && d.kl >= 128) return kFormW64;
     }
     if (b16 && (E == 64 || E == 128)) {
@@ -231,8 +205,6 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
         // prologue).  Masked mode needs the per-tile validity words in LDS (KL <= 64 Ki), the pair-bias mode stays on the
         // 32-row kernel.  Knob kTuneFwdW64: 0 never, 1 wherever instantiated, auto = the rule below.
         const int w64 = tune_get(kTuneFwdW64);
-        // (its LDS-DMA addresses a (batch, kv-head) tensor through a 32-bit buffer offset)
-        const bool fits = mode != 2 && (mode == 0 || d.kl <= 64 * kMaxMaskTiles) && (long long)d.kl * E * 2 < (1LL << 32);
         const bool masked = mode == 1;
         const bool pays = E == 128 ? (d.kl >= 256 && (wg256 >= 160 || (masked && wg256 >= 64)))
                                    : (masked ? (d.kl >= 512 && wg256 >= 128) : (d.kl >= 256 && wg256 >= 64));
@@ -249,9 +221,8 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
             // (L2048 H8 B2: 54.0 -> 33.4 us; L4096 H8 B1: 97.2 -> 57.8; L8192 H8 B1: 189 -> 135), and still ahead up to two rounds in
             // masked mode from KL = 2048 (causal L2048 H8 B4: 56.6 -> 44.3; lens L2048 B4: 68.8 -> 62.4).  KL = 256: a tie.
             const int duo = tune_get(kTuneFwdDuo);
-            const long long w1 = (long long)((d.ql + 127) / 128) * d.qh * d.batch;
             const long long cus = device_cu_count() > 0 ? device_cu_count() : 256;
-            const bool duo_pays = d.kl >= 512 && (w1 <= cus || (masked && d.kl >= 2048 && w1 <= 2 * cus));
+            const bool duo_pays = d.kl >= 512 && (wg128 <= cus || (masked && d.kl >= 2048 && wg128 <= 2 * cus));
             if (duo >= 1 || (duo < 0 && w64 != 1 && duo_pays)) return kFormDuo;
         }
         if (E == 64 && fits && tune_get(kTuneFwdExactScale) != 0) {
@@ -263,7 +234,7 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
         }
         if (fits && (w64 == 1 || (w64 < 0 && pays))) return kFormW64;
     }
-    if (b16 && E == 32 && mode != 2 && (mode == 0 || d.kl <= 64 * kMaxMaskTiles) && (long long)d.kl * E * 2 < (1LL << 32)) {
+    if (b16 && E == 32 && fits) {
         // E = 32: the two-waves-per-SIMD form with 64-row waves (fa_fwd_duo.hpp).  The softmax, not the matrix pipe, is the bound of every
         // form at E = 32 (they take as long as at E = 64).  Measured (profiles/r04/duo32_sweep.log), grids of >= 256 blocks: masked mode
         // 1.1-1.5x faster from KL = 1024 (causal L2048 H8 B8 61.2 -> 40.8 us, L4096 H8 B8 164 -> 125; key padding +2..12 %), plain mode
@@ -282,21 +253,10 @@ static inline int fwd_form_of(const nnop_fa_desc& d, int mode, bool windowed = f
 
 template <typename T, int E>
 static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
-    const bool capped = a.softcap != 0.f;
-    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr, a.win.on() || capped);
-    if (capped) {
-        // logit soft-capping: the CAP instantiations of the windowed body, same shape; without a window its bounds stay -1 (unbounded)
-        return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true, true>(d, a, s);
-    }
-    if (a.win.on()) {
-        // sliding window: the 32-row kernel's WIN body, 4 waves (128-row workgroups: a block's rows span less of the window, and a
-        // windowed grid has as many blocks as the causal one)
-        return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true>(d, a, s);
-    }
-    const int form = fwd_form_of(d, mode, false);
-    // Workgroup shape of the 32-row form: 8 waves x 32 rows (256-row workgroups) when that still yields >= one
-    // workgroup per CU, else 4 waves x 32 rows so that small problems spread over more CUs.
-    const long long wg256 = (long long)((d.ql + 255) / 256) * d.qh * d.batch;
+    const bool win_on = a.win.on(), capped = a.softcap != 0.f;
+    const int mode = fwd_mode(d, a.pair != nullptr, a.kpad != nullptr, win_on, capped);
+    const long long wg256 = fwd_wg(d, 256), wg128 = fwd_wg(d, 128);
+    const int form = fwd_form_of(d, mode, win_on, capped, wg256, wg128);
     if constexpr (sizeof(T) == 2 && E == 256) {
         if (form == kFormW64) return mode == 0 ? launch_fwd_w64<T, E, 0, false>(d, a, s) : launch_fwd_w64<T, E, 1, false>(d, a, s);    // exact scale only
     }
@@ -329,6 +289,16 @@ static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) 
     if constexpr (sizeof(T) == 2 && E <= 64) {
         if (form == kFormSplit) return launch_fwd_split<T, E>(d, a, s);
     }
+    // kFormRow32
+    if (win_on || capped) {
+        // sliding window: the 32-row kernel's WIN body, 4 waves (128-row workgroups: a block's rows span less of the window, and a
+        // windowed grid has as many blocks as the causal one).  Logit soft-capping: the CAP instantiations of that body, same shape;
+        // without a window its bounds stay -1 (unbounded)
+        if (capped) return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true, true>(d, a, s);
+        return mode == 2 ? launch_fwd_cfg<T, E, 4, 2, 1, true>(d, a, s) : launch_fwd_cfg<T, E, 4, 1, 1, true>(d, a, s);
+    }
+    // Workgroup shape of the 32-row form: 8 waves x 32 rows (256-row workgroups) when that still yields >= one
+    // workgroup per CU, else 4 waves x 32 rows so that small problems spread over more CUs.
     int nw = 8, qb = 1;
     if (wg256 < 256 || d.ql <= 128) nw = 4;
     // causal, E <= 64: the waves of a 256-row workgroup see 1..4 x the keys of its first wave and wait for the last one
@@ -337,14 +307,10 @@ static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) 
     // equal (C3: 5.60 vs 5.62-5.70 ms) or better (C5 shard: 20.4 vs 21.2-21.6 ms).
     // At E = 128 only for short sequences (QL <= 2048: L1024 314 -> 269 us, L2048 485 -> 469 us; from L4096 on the 8-wave
     // form wins: 723 vs 762-858 us).
-    {
-        const long long wg128 = (long long)((d.ql + 127) / 128) * d.qh * d.batch;
-        if (d.causal && wg128 >= 512 && (E <= 64 || d.ql <= 2048)) nw = 4;
-    }
+    if (d.causal && wg128 >= 512 && (E <= 64 || d.ql <= 2048)) nw = 4;
     // fp32 E = 128 under a causal mask: two 4-wave workgroups fit a CU where one 8-wave workgroup does, and with the alternating block order
     // (launch_fwd_cfg) they pair heavy with light: L4096 H8 B2 1019.6 -> 627.0 us.  Only where that order applies.
     if constexpr (sizeof(T) == 4 && E == 128) {
-        const long long wg128 = (long long)((d.ql + 127) / 128) * d.qh * d.batch;
         if (mode == 1 && causal_alt_run(d.causal != 0, wg128, (long long)d.qh * d.batch, d.qh / d.kh, (d.ql + 127) / 128) > 0) nw = 4;
     }
     if (E >= 128 && mode == 2) nw = 4;               // the E=128 pair-bias body: 4 waves per workgroup
@@ -359,27 +325,18 @@ static int launch_fwd_e(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) 
     }
 #endif
     if constexpr (E < 256) {
-        if (nw == 8) return launch_fwd_mode<T, E, 8, 1>(d, a, s, mode);
+        if (nw == 8) return mode == 0 ? launch_fwd_cfg<T, E, 8, 0, 1>(d, a, s) : mode == 1 ? launch_fwd_cfg<T, E, 8, 1, 1>(d, a, s) : launch_fwd_cfg<T, E, 8, 2, 1>(d, a, s);
     }
-    return launch_fwd_mode<T, E, 4, 1>(d, a, s, mode);
+    return mode == 0 ? launch_fwd_cfg<T, E, 4, 0, 1>(d, a, s) : mode == 1 ? launch_fwd_cfg<T, E, 4, 1, 1>(d, a, s) : launch_fwd_cfg<T, E, 4, 2, 1>(d, a, s);
 }
 
 template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
     FwdParams p;
-    p.o = a.o; p.ms = a.ms; p.ls = a.ls;
-    p.q = a.q; p.k = a.k; p.v = a.v; p.pair = a.pair; p.kpad = a.kpad;
-    p.sinks = a.sinks;
-    p.QL = d.ql; p.KL = d.kl; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
-    p.causal = d.causal ? 1 : 0;
-    p.win_left = a.win.left; p.win_right = a.win.right;
-    p.n_qblk = 0; p.n_wg = 0;
-    p.scale = (float)(1.0 / sqrt((double)d.emb));
+    fwd_params(p, d, a, 0);
     const long long n_rows = (long long)d.batch * d.qh * d.ql;
     const long long grid = (n_rows + 3) / 4;
     if (grid > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     if (a.softcap != 0.f) {
-        const SoftcapK ck = softcap_k(1.0 / sqrt((double)d.emb), a.softcap);
-        p.cap_ka = ck.ka; p.cap_kb = ck.kb;
         if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_cap_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
         else hipLaunchKernelGGL((fa_fwd_generic_cap_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
     } else

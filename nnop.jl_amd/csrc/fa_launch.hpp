@@ -58,11 +58,10 @@ template <typename T> int launch_fwd(const nnop_fa_desc& d, const FwdArgs& a, hi
 // Which kernel form launch_fwd picks (no launch): 0 = 32-row waves, 1 = split-KV, 2 = 64-row waves, 3 = the plain-HIP kernel of
 // fa_generic.hpp (embedding dims outside the tiled set), 4 = two waves per SIMD in alternating phases (fa_fwd_duo.hpp).
 enum FwdForm { kFormRow32 = 0, kFormSplit = 1, kFormW64 = 2, kFormGeneric = 3, kFormDuo = 4 };
-// A windowed problem (FaWindow::on) always runs kFormRow32 or kFormGeneric, and so does a capped one (softcap != 0): callers pass
-// `windowed` = window on or cap on.
-int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool windowed = false);
+// A windowed problem (win_on = FaWindow::on) always runs kFormRow32 or kFormGeneric, and so does a capped one (capped = softcap != 0).
+int fwd_form(const nnop_fa_desc& d, bool has_pair, bool has_mask, bool win_on, bool capped);
 // Which backward kernels launch_bwd picks (no launch): bit 0: dK/dV on fa_bwd_w64_kernel, bit 1: dQ on it (else fa_bwd.hpp's)
-int bwd_forms(const nnop_fa_desc& d, bool has_pair, bool windowed = false);
+int bwd_forms(const nnop_fa_desc& d, bool has_pair, bool win_on, bool capped);
 // One per dtype (fa_bwd_{f32,f16,bf16}.hip).
 template <typename T> int launch_bwd(const nnop_fa_desc& d, const BwdArgs& a, hipStream_t s);
 // dsinks from dO, o, ms, ls alone, whichever backward kernels ran (fa_sinks.hpp); uses the workspace, after launch_bwd on the same stream.
@@ -169,6 +168,23 @@ inline bool small_grid_prefers_32_row_waves(int len, long long cols, bool causal
     if (causal) return 2 * w2 <= 3 * cus;
     const long long r2 = (w2 + cus - 1) / cus, r1 = (w1 + cus - 1) / cus;
     return 62 * r1 < 100 * r2;
+}
+
+// Persistent form of the one-wave / two-wave kernels (fa_fwd_w64.hpp, fa_fwd_duo.hpp, fa_bwd_w64.hpp): 256 workgroups that each walk
+// `steps` blocks of a static, balanced list instead of one workgroup per block -- on a 256-CU device, when the list divides: `cols`
+// (batch x head) columns in eighths (one per XCD), a power-of-two number `n_blk` of blocks per column, whole steps of 32 blocks per XCD,
+// and more than one step.  `knob`: 0 never, 1 wherever it divides, auto = where the caller measured that it `pays`.  steps = 0: one
+// block per workgroup.  hx: heads per XCD when the `heads` of the column axis divide by 8 (batch-major columns), else 0.
+struct PersistList { int steps = 0, hx = 0; };
+inline PersistList persist_list(long long cols, int heads, int n_blk, int knob, bool pays) {
+    PersistList l;
+    const long long per_xcd = (cols / 8) * n_blk;
+    if ((knob == 1 || (knob < 0 && pays)) && device_cu_count() == 256 && cols % 8 == 0 && (n_blk & (n_blk - 1)) == 0 &&
+        per_xcd % 32 == 0 && per_xcd / 32 >= 2 && per_xcd / 32 <= (1 << 24)) {
+        l.steps = (int)(per_xcd / 32);
+        l.hx = heads % 8 == 0 ? heads / 8 : 0;
+    }
+    return l;
 }
 
 // Kernels that need more than 64 KiB of dynamic LDS must opt in once per (kernel, device).  `done` is a per-kernel

@@ -94,44 +94,32 @@ int nnop_debug_set(int key, int value) {
     if (!__atomic_load_n(&g_debug_hooks, __ATOMIC_RELAXED)) return INT_MIN;
     return __atomic_exchange_n(&g_tune[key], value, __ATOMIC_RELAXED);
 }
+// (one body per direction, the _cap one: the narrower hooks are it without a cap / without options, as nnop_fa_fwd is nnop_fa_fwd_softcap)
 int nnop_debug_fwd_form(const nnop_fa_desc* d, int has_pair, int has_mask) {
-    const int st = check_desc(d);
-    if (st != NNOP_OK) return st;
-    return fwd_form(*d, has_pair != 0, has_mask != 0);
+    return nnop_debug_fwd_form_cap(d, nullptr, 0.f, has_pair, has_mask);
 }
 int nnop_debug_bwd_form(const nnop_fa_desc* d, int has_pair, int has_mask) {
-    const int st = check_desc(d);
-    if (st != NNOP_OK) return st;
-    (void)has_mask;
-    return bwd_forms(*d, has_pair != 0);
+    return nnop_debug_bwd_form_cap(d, nullptr, 0.f, has_pair, has_mask);
 }
 int nnop_debug_fwd_form_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, int has_pair, int has_mask) {
-    int st = check_desc(d);
-    if (st == NNOP_OK) st = check_opts(opts);
-    if (st != NNOP_OK) return st;
-    return fwd_form(*d, has_pair != 0, has_mask != 0, fa_window(*d, opts).on());
+    return nnop_debug_fwd_form_cap(d, opts, 0.f, has_pair, has_mask);
 }
 int nnop_debug_bwd_form_ex(const nnop_fa_desc* d, const nnop_fa_opts* opts, int has_pair, int has_mask) {
-    int st = check_desc(d);
-    if (st == NNOP_OK) st = check_opts(opts);
-    if (st != NNOP_OK) return st;
-    (void)has_mask;
-    return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on());
+    return nnop_debug_bwd_form_cap(d, opts, 0.f, has_pair, has_mask);
 }
 int nnop_debug_fwd_form_cap(const nnop_fa_desc* d, const nnop_fa_opts* opts, float softcap, int has_pair, int has_mask) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
     if (st == NNOP_OK) st = check_softcap(softcap);
     if (st != NNOP_OK) return st;
-    return fwd_form(*d, has_pair != 0, has_mask != 0, fa_window(*d, opts).on() || softcap != 0.f);
+    return fwd_form(*d, has_pair != 0, has_mask != 0, fa_window(*d, opts).on(), softcap != 0.f);
 }
-int nnop_debug_bwd_form_cap(const nnop_fa_desc* d, const nnop_fa_opts* opts, float softcap, int has_pair, int has_mask) {
+int nnop_debug_bwd_form_cap(const nnop_fa_desc* d, const nnop_fa_opts* opts, float softcap, int has_pair, int) {
     int st = check_desc(d);
     if (st == NNOP_OK) st = check_opts(opts);
     if (st == NNOP_OK) st = check_softcap(softcap);
     if (st != NNOP_OK) return st;
-    (void)has_mask;
-    return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on() || softcap != 0.f);
+    return bwd_forms(*d, has_pair != 0, fa_window(*d, opts).on(), softcap != 0.f);
 }
 int nnop_debug_dev_build(void) {
 #ifdef NNOP_DEV_BUILD

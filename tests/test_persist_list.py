@@ -1,5 +1,5 @@
 """CPU: the static block list of the persistent kernels (csrc/fa_fwd_w64.hpp "persistent form", csrc/fa_bwd_w64.hpp, launch rule in
-csrc/fa_fwd_inst.hpp launch_fwd_w64 / csrc/fa_bwd_inst.hpp launch_bwd_w64), restated here to pin its two properties: every block of
+csrc/fa_launch.hpp persist_list, which launch_fwd_w64, launch_fwd_duo and launch_bwd_w64 ask), restated here to pin its two properties: every block of
 the problem is visited exactly once, and under a causal mask every workgroup gets the same work.  (That the KERNELS walk this list is
 what the GPU tests check: bitwise equality with the one-block-per-workgroup launch, tests/test_fwd_w64_gpu.py / test_bwd_w64_gpu.py.)"""
 import numpy as np

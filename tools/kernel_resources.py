@@ -3,8 +3,10 @@
 
 A change that adds kernel variants must leave the kernels that existed before as they were.  For every kernel symbol of the
 PARENT library this reads the code objects' AMDGPU metadata notes (what the loader itself goes by) in both libraries and compares
-VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, static LDS bytes and the wavefront size.  Exit status 1 when a parent kernel is
-missing from the new library or a figure differs; kernels that only the new library has are listed with their figures.
+VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, static LDS bytes and the wavefront size, and a hash of the kernel's machine-code
+bytes (the function symbol's range in the code object: register figures alone do not show that no instruction moved).  Exit status 1
+when a parent kernel is missing from the new library or a figure differs; kernels that only the new library has are listed with
+their figures (a host-only change must report new: 0 as well).
 
     python tools/kernel_resources.py --parent /path/to/parent/libnnop_hip.so [--this nnop.jl_amd/lib/libnnop_hip.so]
                                      [--out profiles/r05/kernel_resources.txt] [--new-only-filter cap]
@@ -13,6 +15,7 @@ The code objects are found inside the host library's fat binary by their ELF hea
 Makefile builds); the notes are read with llvm-readelf from $ROCM_PATH/llvm/bin (default /opt/rocm).
 """
 import argparse
+import hashlib
 import os
 import re
 import struct
@@ -47,14 +50,36 @@ def code_objects(path):
     return out
 
 
+def code_hashes(img):
+    """{function symbol: first 16 hex digits of the SHA-256 of its machine-code bytes} from one code object's symbol table"""
+    shoff, = struct.unpack_from("<Q", img, 40)
+    shentsize, shnum = struct.unpack_from("<HH", img, 58)
+    # section header: name, type, flags, addr, offset, size, link, info, addralign, entsize
+    secs = [struct.unpack_from("<IIQQQQIIQQ", img, shoff + i * shentsize) for i in range(shnum)]
+    out = {}
+    for _, typ, _, _, off, size, link, _, _, entsize in secs:
+        if typ != 2:                                          # SHT_SYMTAB
+            continue
+        str_off = secs[link][4]
+        for i in range(size // entsize):
+            name, info, _, shndx, value, sz = struct.unpack_from("<IBBHQQ", img, off + i * entsize)
+            if (info & 15) != 2 or sz == 0 or shndx == 0 or shndx >= shnum:      # STT_FUNC, defined
+                continue
+            end = img.index(b"\0", str_off + name)
+            start = secs[shndx][4] + value - secs[shndx][3]
+            out[img[str_off + name:end].decode()] = hashlib.sha256(img[start:start + sz]).hexdigest()[:16]
+    return out
+
+
 def readelf():
     return os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf")
 
 
 def kernels(path):
-    """{demangled-free symbol name: {field: int}} over all code objects of the library"""
+    """{demangled-free symbol name: {field: int, "code": hash}} over all code objects of the library"""
     res = {}
     for img in code_objects(path):
+        hashes = code_hashes(img)
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(img)
             f.flush()
@@ -71,12 +96,13 @@ def kernels(path):
             for key, tag in FIELDS:
                 v = re.search(r"\n?\s" + re.escape(tag) + r":\s+(\d+)", block)
                 rec[key] = int(v.group(1)) if v else 0
+            rec["code"] = hashes.get(name.group(1), "none")
             res[name.group(1)] = rec
     return res
 
 
 def fmt(rec):
-    return " ".join(f"{k}={rec[k]}" for k, _ in FIELDS)
+    return " ".join(f"{k}={rec[k]}" for k, _ in FIELDS) + f" code={rec['code']}"
 
 
 def main():
@@ -94,7 +120,7 @@ def main():
     added = sorted(n for n in new if n not in old)
     lines.append(f"parent kernels: {len(old)}   this build: {len(new)}   missing: {len(missing)}   differing: {len(differ)}   "
                  f"identical: {len(old) - len(missing) - len(differ)}   new: {len(added)}")
-    lines.append("fields: " + ", ".join(k for k, _ in FIELDS))
+    lines.append("fields: " + ", ".join(k for k, _ in FIELDS) + ", code (hash of the machine-code bytes)")
     for n in missing:
         lines.append(f"MISSING {n}")
     for n in differ:
