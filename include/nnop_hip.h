@@ -328,6 +328,35 @@ int nnop_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* db, c
 size_t nnop_norm_bwd_workspace_bytes(const nnop_norm_desc* d, int layer_norm);
 
 /*
+ * Residual add fused into RMSNorm / LayerNorm (no counterpart in the reference; the pre-norm block's `h = x + residual;
+ * y = norm(h)` in one pass over memory: 4 row-sized arrays moved instead of 5 forward, 4 instead of 6 in the pullback).
+ *   add_rms_norm(x, residual, w; ϵ, offset) -> (y, h, rms)        add_layer_norm(x, residual, w, b; ϵ) -> (y, h, μ, Σ)
+ * Forward:  h = T(fp32(x) + fp32(residual)) -- one fp32 add, one rounding to the element type T -- is written out, and the
+ * statistics and y are those of the plain operator applied to the ROUNDED h: rms / mu, sigma / y are what nnop_rms_norm /
+ * nnop_layer_norm return for input h, so the pullback, which reads h from memory, sees exactly what the forward normalised.
+ * x, residual, h, y : [n][emb] of `dtype`;  w, b, offset, eps, the statistics and the w_dtype rules: as for the plain operators
+ * (same nnop_norm_desc, same validation).  h may be the same buffer as x or as residual (same base address: the in-place
+ * update of the residual stream); partial overlap is undefined.  y must not overlap an input.
+ * Pullback: dy is the cotangent of y, dh the cotangent of h (what the rest of the residual stream sends back; may be NULL).
+ * ONE gradient dx is written, the gradient of x and of residual alike (they are equal):  dx = T(g + fp32(dh)), g being the
+ * fp32, not yet rounded, input gradient the plain pullback computes from (dy, h, w, statistics) -- one rounding, not two.
+ * dw (and db) are exactly the plain pullback's (fp32 [emb] for RMSNorm, `w_dtype` for LayerNorm; same partial rows, same
+ * fixed-order fold, no atomics).  dh == NULL gives exactly the results of nnop_rms_norm_bwd / nnop_layer_norm_bwd on h.
+ * dx may be the same buffer as dh (accumulate into the stream's gradient).  Workspace: nnop_norm_bwd_workspace_bytes().
+ * Checks, in this order: descriptor, NULL pointers (dh exempt), workspace size.
+ */
+int nnop_add_rms_norm(const nnop_norm_desc* d, void* y, void* h, float* rms, const void* x, const void* residual,
+                      const void* w, float offset, float eps, nnop_stream_t stream);
+int nnop_add_rms_norm_bwd(const nnop_norm_desc* d, void* dx, float* dw, const void* dy, const void* dh /* may be NULL */,
+                          const float* rms, const void* h, const void* w, float offset,
+                          void* workspace, size_t workspace_bytes, nnop_stream_t stream);
+int nnop_add_layer_norm(const nnop_norm_desc* d, void* y, void* h, float* mu, float* sigma, const void* x,
+                        const void* residual, const void* w, const void* b, float eps, nnop_stream_t stream);
+int nnop_add_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* db, const void* dy,
+                            const void* dh /* may be NULL */, const float* mu, const float* sigma, const void* h,
+                            const void* w, void* workspace, size_t workspace_bytes, nnop_stream_t stream);
+
+/*
  * Sharding over several devices (ABI version 6).  The reference has no multi-GPU code; its (batch, kv-head) slices -- a KV head with its
  * QH / KH query heads -- are independent in forward and backward (src/attention.jl:27-28,33; src/attention_bwd.jl:28-29,34), so a host
  * that owns several devices gives rank g of `world` the contiguous unit range [g U / world, (g+1) U / world), U = batch * kh, units

@@ -54,6 +54,10 @@ EXPORTED_SYMBOLS = (
     "nnop_layer_norm",
     "nnop_layer_norm_bwd",
     "nnop_norm_bwd_workspace_bytes",
+    "nnop_add_rms_norm",
+    "nnop_add_rms_norm_bwd",
+    "nnop_add_layer_norm",
+    "nnop_add_layer_norm_bwd",
     "nnop_fa_shards",
     "nnop_shared_memory",
     "nnop_strerror",
@@ -181,6 +185,14 @@ def load():
     lib.nnop_layer_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.nnop_norm_bwd_workspace_bytes.restype = C.c_size_t
     lib.nnop_norm_bwd_workspace_bytes.argtypes = [nd, C.c_int]
+    lib.nnop_add_rms_norm.restype = C.c_int
+    lib.nnop_add_rms_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    lib.nnop_add_rms_norm_bwd.restype = C.c_int
+    lib.nnop_add_rms_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, C.c_size_t, vp]
+    lib.nnop_add_layer_norm.restype = C.c_int
+    lib.nnop_add_layer_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]
+    lib.nnop_add_layer_norm_bwd.restype = C.c_int
+    lib.nnop_add_layer_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.nnop_fa_shards.restype = C.c_int
     lib.nnop_fa_shards.argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int, C.POINTER(FaShard)]
     lib.nnop_shared_memory.restype = C.c_int

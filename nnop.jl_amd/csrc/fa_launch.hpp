@@ -83,6 +83,15 @@ int launch_layer_norm(const nnop_norm_desc& d, void* y, float* mu, float* sigma,
                       const void* b, float eps, hipStream_t s);
 int launch_layer_norm_bwd(const nnop_norm_desc& d, void* dx, void* dw, void* db, const void* dy, const float* mu,
                           const float* sigma, const void* x, const void* w, void* ws, hipStream_t s);
+// fused residual add: h = T(x + residual) is written and normalised; the pullbacks add dh (NULL: the plain pullback) into dx
+int launch_add_rms_norm(const nnop_norm_desc& d, void* y, void* h, float* rms, const void* x, const void* residual,
+                        const void* w, float offset, float eps, hipStream_t s);
+int launch_add_rms_norm_bwd(const nnop_norm_desc& d, void* dx, float* dw, const void* dy, const void* dh, const float* rms,
+                            const void* h, const void* w, float offset, void* ws, hipStream_t s);
+int launch_add_layer_norm(const nnop_norm_desc& d, void* y, void* h, float* mu, float* sigma, const void* x,
+                          const void* residual, const void* w, const void* b, float eps, hipStream_t s);
+int launch_add_layer_norm_bwd(const nnop_norm_desc& d, void* dx, void* dw, void* db, const void* dy, const void* dh,
+                              const float* mu, const float* sigma, const void* h, const void* w, void* ws, hipStream_t s);
 size_t norm_ws_bytes(const nnop_norm_desc& d, bool ln);
 
 // Embedding dims the MFMA kernels are instantiated for.

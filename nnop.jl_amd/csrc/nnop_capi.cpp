@@ -317,6 +317,42 @@ int nnop_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* db, c
     return launch_layer_norm_bwd(*d, dx, dw, db, dy, mu, sigma, x, w, workspace, (hipStream_t)stream);
 }
 
+int nnop_add_rms_norm(const nnop_norm_desc* d, void* y, void* h, float* rms, const void* x, const void* residual,
+                      const void* w, float offset, float eps, nnop_stream_t stream) {
+    const int st = check_norm(d);
+    if (st != NNOP_OK) return st;
+    if (!y || !h || !rms || !x || !residual || !w) return NNOP_ERR_NULL;
+    return launch_add_rms_norm(*d, y, h, rms, x, residual, w, offset, eps, (hipStream_t)stream);
+}
+
+int nnop_add_rms_norm_bwd(const nnop_norm_desc* d, void* dx, float* dw, const void* dy, const void* dh, const float* rms,
+                          const void* h, const void* w, float offset, void* workspace, size_t workspace_bytes,
+                          nnop_stream_t stream) {
+    const int st = check_norm(d);
+    if (st != NNOP_OK) return st;
+    if (!dx || !dw || !dy || !rms || !h || !w || !workspace) return NNOP_ERR_NULL;      // dh may be NULL
+    if (workspace_bytes < norm_ws_bytes(*d, false)) return NNOP_ERR_WORKSPACE;
+    return launch_add_rms_norm_bwd(*d, dx, dw, dy, dh, rms, h, w, offset, workspace, (hipStream_t)stream);
+}
+
+int nnop_add_layer_norm(const nnop_norm_desc* d, void* y, void* h, float* mu, float* sigma, const void* x,
+                        const void* residual, const void* w, const void* b, float eps, nnop_stream_t stream) {
+    const int st = check_norm(d);
+    if (st != NNOP_OK) return st;
+    if (!y || !h || !mu || !sigma || !x || !residual || !w || !b) return NNOP_ERR_NULL;
+    return launch_add_layer_norm(*d, y, h, mu, sigma, x, residual, w, b, eps, (hipStream_t)stream);
+}
+
+int nnop_add_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* db, const void* dy, const void* dh,
+                            const float* mu, const float* sigma, const void* h, const void* w, void* workspace,
+                            size_t workspace_bytes, nnop_stream_t stream) {
+    const int st = check_norm(d);
+    if (st != NNOP_OK) return st;
+    if (!dx || !dw || !db || !dy || !mu || !sigma || !h || !w || !workspace) return NNOP_ERR_NULL;   // dh may be NULL
+    if (workspace_bytes < norm_ws_bytes(*d, true)) return NNOP_ERR_WORKSPACE;
+    return launch_add_layer_norm_bwd(*d, dx, dw, db, dy, dh, mu, sigma, h, w, workspace, (hipStream_t)stream);
+}
+
 size_t nnop_norm_bwd_workspace_bytes(const nnop_norm_desc* d, int layer_norm) {
     if (check_norm(d) != NNOP_OK) return 0;
     return norm_ws_bytes(*d, layer_norm != 0);

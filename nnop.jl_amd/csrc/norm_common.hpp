@@ -14,6 +14,7 @@
 // and every lane owns fixed columns, so dw/db accumulate in REGISTERS; the <= 1024 partial rows are folded by one small
 // second kernel in a fixed order (deterministic, no atomics).
 // Bound: HBM -- forward 2*emb*sizeof(T) per row; pullback 3*emb*sizeof(T) per row (+ the partials, <= 8 %).
+// With the residual add fused in (ADD = true, below): 4*emb*sizeof(T) per row in both directions, against 5 and 6 as two calls.
 #pragma once
 #include "row_common.hpp"
 #include "fa_launch.hpp"
@@ -35,7 +36,25 @@ struct NormParams {
     long long n;
     float offset, eps, inv_emb;
     int n_groups;             // pullback: row stride of a group
+    // fused residual add (ADD = true kernels only; behind every field the plain kernels read)
+    const void* r;            // forward: residual;  pullback: dh, the cotangent of h
+    void* h;                  // forward: h = T(x + residual), written out; may be the buffer of a or of r
 };
+
+// Fused residual add (include/nnop_hip.h, nnop_add_rms_norm): ADD = true variants of the four kernels below.
+//   forward   h = T(fp32(x) + fp32(residual)), stored; statistics and y are those of the ROUNDED h (the register row holds T)
+//   pullback  dx = T(g + fp32(dh)), g the fp32 input gradient the plain pullback rounds: one rounding
+// Aliasing (h on x or residual, dx on dh): a lane of the register kernels loads its chunk of a row before it stores that
+// chunk and no other lane touches it; the generic kernels index the same way in every pass and take the buffers that may
+// alias through plain pointers (AliasPtr), reading h back from h.
+// g + dh as an add of its own: never contracted with the multiply that produced g into one fma, so g is the very fp32 value
+// the plain pullback rounds (the contract of include/nnop_hip.h)
+NNOP_DEV float add_dh(float g, float dh) {
+#pragma clang fp contract(off)
+    return g + dh;
+}
+template <typename T, bool ADD> struct AliasPtr { typedef T* __restrict__ type; };
+template <typename T> struct AliasPtr<T, true> { typedef T* type; };
 
 // VEC consecutive elements of a [emb] vector of type W starting at e, as fp32
 template <typename W, int VEC> NNOP_DEV void load_vec(const W* __restrict__ w, int e, float (&out)[VEC]) {
@@ -50,8 +69,13 @@ template <typename W, int VEC> NNOP_DEV void load_vec(const W* __restrict__ w, i
     }
 }
 
+// The lane index as a value the compiler cannot relate to `lane`.  A kernel phase that derives its per-chunk offsets from it
+// computes them anew (one VALU op each) where it would otherwise keep the C offsets of an earlier phase alive: the fused
+// forward has four such phases and, at 16 chunks, no registers to carry offsets between them.
+NNOP_DEV int fresh_lane(int lane) { asm volatile("" : "+v"(lane)); return lane; }
+
 // ---- forward ---------------------------------------------------------------------------------------------------
-template <typename T, typename W, int G, int C, bool LN>
+template <typename T, typename W, int G, int C, bool LN, bool ADD = false>
 __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_fwd_kernel(const NormParams p) {
     constexpr int RPB = G >= 256 ? 1 : 256 / G;
     constexpr int VEC = RowRegs<T, G, C>::VEC;
@@ -62,6 +86,30 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_fwd_k
     const size_t off = (size_t)row * p.emb;
     RowRegs<T, G, C> r;
     r.load((const T*)p.a + off, p.emb, lane, 0.f);
+    if constexpr (ADD) {
+        // the residual row passes through in slices of STEP chunks: the 16-chunk shape has no room for two whole rows
+        constexpr int STEP = C > 8 ? 4 : C;
+        const int lane_h = fresh_lane(lane);
+#pragma unroll
+        for (int j0 = 0; j0 < C; j0 += STEP) {
+            // a slice's loads stay behind the previous slice's adds (its guards equal those of x's loads: without the fence
+            // the compiler merges the guarded blocks and has both rows in flight at once)
+            if constexpr (C > STEP) asm volatile("" ::: "memory");
+            RowRegs<T, G, STEP> res;                           // chunks j0 .. j0 + STEP - 1 of the row
+            res.load((const T*)p.r + off + (size_t)j0 * G * VEC, p.emb - j0 * G * VEC, lane_h, 0.f);
+#pragma unroll
+            for (int j = 0; j < STEP; ++j)
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) r.set(j0 + j, i, r.get(j0 + j, i) + res.get(j, i));      // past emb: 0 + 0
+            if constexpr (C > STEP) {                          // ... and the adds in front of the next slice's loads
+#pragma unroll
+                for (int j = 0; j < STEP; ++j) asm volatile("" : "+v"(r.raw[j0 + j]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        r.store((T*)p.h + off, p.emb, lane_h);                 // both loads of this lane's chunks precede their store
+        repack(r);                                             // everything below sees the rounded h
+    }
     float mu = 0.f;
     if constexpr (LN) {
         float s = 0.f;
@@ -86,9 +134,10 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_fwd_k
         else p.stat0[row] = rstd;
     }
     repack(r);
+    const int lane_y = ADD ? fresh_lane(lane) : lane;
 #pragma unroll
     for (int j = 0; j < C; ++j) {
-        const int e = (j * G + lane) * VEC;
+        const int e = (j * G + lane_y) * VEC;
         if (e < p.emb) {
             float wv[VEC], bv[VEC];
             load_vec<W, VEC>((const W*)p.w, e, wv);
@@ -100,15 +149,22 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_fwd_k
             }
         }
     }
-    r.store((T*)p.out + off, p.emb, lane);
+    r.store((T*)p.out + off, p.emb, lane_y);
 }
 
 // any emb: workgroup per row, element accesses, the reference's pass structure
-template <typename T, typename W, bool LN>
+template <typename T, typename W, bool LN, bool ADD = false>
 __global__ __launch_bounds__(256) void norm_fwd_generic_kernel(const NormParams p) {
     __shared__ float slots[2][4];
     const long long row = blockIdx.x;
-    const T* __restrict__ x = (const T*)p.a + (size_t)row * p.emb;
+    // ADD: the passes below read h back from h; a lane reads only the elements it wrote itself (same stride in every pass)
+    typename AliasPtr<const T, ADD>::type x = (const T*)(ADD ? p.h : p.a) + (size_t)row * p.emb;
+    if constexpr (ADD) {
+        const T* xa = (const T*)p.a + (size_t)row * p.emb;
+        const T* xr = (const T*)p.r + (size_t)row * p.emb;
+        T* h = (T*)p.h + (size_t)row * p.emb;
+        for (int e = threadIdx.x; e < p.emb; e += 256) h[e] = from_f32<T>(to_f32(xa[e]) + to_f32(xr[e]));
+    }
     T* __restrict__ y = (T*)p.out + (size_t)row * p.emb;
     const W* __restrict__ w = (const W*)p.w;
     const W* __restrict__ b = (const W*)p.b;
@@ -133,10 +189,23 @@ __global__ __launch_bounds__(256) void norm_fwd_generic_kernel(const NormParams 
 }
 
 // ---- pullback --------------------------------------------------------------------------------------------------
-template <typename T, typename W, int G, int C, bool LN>
+// When the fused pullback requests a row of dh.  2: a row ahead, beside d_nx / x_nx (six rows live).  The widest shape (1024
+// lanes x 16 columns) is at its register limit with four rows and would spill where the plain kernel does not, so there --
+// 1: at the top of the row's own iteration, in front of the reduction, which still hides most of the latency.
+template <typename T, int G, int C> constexpr bool norm_bwd_widest() { return G == 1024 && C * (16 / (int)sizeof(T)) >= 16; }
+template <typename T, int G, int C> constexpr int norm_bwd_dh_ahead() { return norm_bwd_widest<T, G, C>() ? 1 : 2; }
+// LayerNorm at the widest shape has no room for that fifth row beside w, dw and db: its fused variant reads w from memory in
+// both passes over a row (emb elements from L2, against four rows from HBM) instead of holding it in 16 registers
+template <typename T, int G, int C, bool LN, bool ADD> constexpr bool norm_bwd_w_from_memory() {
+    return ADD && LN && norm_bwd_widest<T, G, C>();
+}
+
+// ADD: dx = T(g + dh)
+template <typename T, typename W, int G, int C, bool LN, bool ADD = false, int PF = norm_bwd_dh_ahead<T, G, C>()>
 __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_kernel(const NormParams p) {
     constexpr int RPB = G >= 256 ? 1 : 256 / G;
     constexpr int VEC = RowRegs<T, G, C>::VEC;
+    constexpr bool WMEM = norm_bwd_w_from_memory<T, G, C, LN, ADD>();
     __shared__ float slots_f[2][G > 64 ? G / 64 : 1];
     __shared__ Sum2 slots_2[2][G > 64 ? G / 64 : 1];
     __shared__ float comb[RPB > 1 ? (LN ? 2 : 1) * 64 * C * VEC : 1];   // wave-per-row shapes: fold the 4 waves
@@ -150,7 +219,7 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
         const int e = (j * G + lane) * VEC;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) { wv[j][i] = 0.f; dw[j][i] = 0.f; if constexpr (LN) db[j][i] = 0.f; }
-        if (e < p.emb) {
+        if (!WMEM && e < p.emb) {
             load_vec<W, VEC>((const W*)p.w, e, wv[j]);
             if constexpr (!LN)
 #pragma unroll
@@ -161,9 +230,11 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
     // the next row's dy / x are requested before the current row's reduce-and-store chain starts: a group otherwise
     // has nothing in flight while it waits on its own reduction
     RowRegs<T, G, C> d, x, d_nx, x_nx;
+    RowRegs<T, ADD ? G : 1, ADD ? C : 1> h, h_nx;                     // dh rows (ADD)
     if (g0 < p.n) {
         d.load((const T*)p.a + (size_t)g0 * p.emb, p.emb, lane, 0.f);
         x.load((const T*)p.x + (size_t)g0 * p.emb, p.emb, lane, 0.f);
+        if constexpr (ADD && PF == 2) h.load((const T*)p.r + (size_t)g0 * p.emb, p.emb, lane, 0.f);
     }
     for (long long row = g0; row < p.n; row += p.n_groups, ++it) {
         const size_t off = (size_t)row * p.emb;
@@ -171,7 +242,9 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
         if (nx < p.n) {
             d_nx.load((const T*)p.a + (size_t)nx * p.emb, p.emb, lane, 0.f);
             x_nx.load((const T*)p.x + (size_t)nx * p.emb, p.emb, lane, 0.f);
+            if constexpr (ADD && PF == 2) h_nx.load((const T*)p.r + (size_t)nx * p.emb, p.emb, lane, 0.f);
         }
+        if constexpr (ADD && PF == 1) h.load((const T*)p.r + off, p.emb, lane, 0.f);
         if constexpr (!LN) {
             const float rstd = p.stat0[row];
             float dd = 0.f;
@@ -187,7 +260,8 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
                 for (int i = 0; i < VEC; ++i) {
                     const float de = d.get(j, i), xe = x.get(j, i);
                     dw[j][i] = __builtin_fmaf(de, xe * rstd, dw[j][i]);                                          // :98,101
-                    d.set(j, i, __builtin_fmaf(de * wv[j][i], rstd, k * xe));                                    // :95-96
+                    const float g = __builtin_fmaf(de * wv[j][i], rstd, k * xe);                                 // :95-96
+                    if constexpr (ADD) d.set(j, i, add_dh(g, h.get(j, i))); else d.set(j, i, g);
                 }
         } else {
             const float mu = p.stat0[row], rstd = p.stat1[row];
@@ -196,6 +270,7 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
 #pragma unroll
             for (int j = 0; j < C; ++j)
                 if (x.in_row(j, lane, p.emb)) {
+                    if constexpr (WMEM) load_vec<W, VEC>((const W*)p.w, (j * G + lane) * VEC, wv[j]);
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
                         const float xn = __builtin_fmaf(x.get(j, i), rstd, nmr), wdy = wv[j][i] * d.get(j, i);  // :102-106
@@ -209,18 +284,21 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
 #pragma unroll
             for (int j = 0; j < C; ++j)
                 if (x.in_row(j, lane, p.emb)) {
+                    if constexpr (WMEM) load_vec<W, VEC>((const W*)p.w, (j * G + lane) * VEC, wv[j]);
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
                         const float de = d.get(j, i);
                         const float xn = __builtin_fmaf(x.get(j, i), rstd, nmr), wdy = wv[j][i] * de;
                         dw[j][i] = __builtin_fmaf(de, xn, dw[j][i]);                                             // :129,132
                         db[j][i] += de;                                                                          // :133
-                        d.set(j, i, __builtin_fmaf(wdy, rstd, __builtin_fmaf(xn, k1, k2)));
+                        const float g = __builtin_fmaf(wdy, rstd, __builtin_fmaf(xn, k1, k2));
+                        if constexpr (ADD) d.set(j, i, add_dh(g, h.get(j, i))); else d.set(j, i, g);
                     }
                 }
         }
-        d.store((T*)p.out + off, p.emb, lane);
+        d.store((T*)p.out + off, p.emb, lane);             // ADD: may be the dh row this lane loaded above
         d = d_nx; x = x_nx;
+        if constexpr (ADD && PF == 2) h = h_nx;
     }
     // fold the workgroup's groups (wave-per-row shapes) in a fixed order, then one partial row per workgroup
     if constexpr (RPB > 1) {
@@ -269,14 +347,15 @@ __global__ __launch_bounds__(G > 256 ? G : 256, G > 256 ? 1 : 2) void norm_bwd_k
 
 // any emb: a workgroup walks rows blockIdx.x, +gridDim.x, ..; a lane owns columns tid, tid+256, .. and accumulates
 // its partial sums directly in its workgroup's partial row (same lane, same address: no race)
-template <typename T, typename W, bool LN>
+template <typename T, typename W, bool LN, bool ADD = false>
 __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormParams p) {
     __shared__ float slots_f[2][4];
     __shared__ Sum2 slots_2[2][4];
     const T* __restrict__ dy = (const T*)p.a;
     const T* __restrict__ xx = (const T*)p.x;
     const W* __restrict__ w = (const W*)p.w;
-    T* __restrict__ dx = (T*)p.out;
+    typename AliasPtr<T, ADD>::type dx = (T*)p.out;
+    const T* dh = (const T*)p.r;                                // ADD: may be dx; element e is read before it is written
     float* pw = p.part_w + (size_t)blockIdx.x * p.emb;
     float* pb = LN ? p.part_b + (size_t)blockIdx.x * p.emb : nullptr;
     for (int e = threadIdx.x; e < p.emb; e += 256) { pw[e] = 0.f; if (LN) pb[e] = 0.f; }
@@ -293,7 +372,8 @@ __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormParams 
             for (int e = threadIdx.x; e < p.emb; e += 256) {
                 const float de = to_f32(dy[off + e]), xe = to_f32(xx[off + e]);
                 pw[e] = __builtin_fmaf(de, xe * rstd, pw[e]);
-                dx[off + e] = from_f32<T>(rstd * (de * (to_f32(w[e]) + p.offset)) + rstd * (k * xe));
+                const float g = rstd * (de * (to_f32(w[e]) + p.offset)) + rstd * (k * xe);
+                if constexpr (ADD) dx[off + e] = from_f32<T>(add_dh(g, to_f32(dh[off + e]))); else dx[off + e] = from_f32<T>(g);
             }
         } else {
             const float mu = p.stat0[row], rstd = p.stat1[row];
@@ -310,7 +390,8 @@ __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormParams 
                 const float xn = (to_f32(xx[off + e]) - mu) * rstd, wdy = to_f32(w[e]) * de;
                 pw[e] = __builtin_fmaf(de, xn, pw[e]);
                 pb[e] += de;
-                dx[off + e] = from_f32<T>((wdy - (xn * c1 + c2)) * rstd);
+                const float g = (wdy - (xn * c1 + c2)) * rstd;
+                if constexpr (ADD) dx[off + e] = from_f32<T>(add_dh(g, to_f32(dh[off + e]))); else dx[off + e] = from_f32<T>(g);
             }
         }
     }
@@ -371,25 +452,26 @@ static inline size_t norm_bwd_ws_bytes(const nnop_norm_desc& d, bool ln) {
     return (size_t)norm_bwd_max_parts(d.n) * (size_t)d.emb * sizeof(float) * (ln ? 2 : 1);
 }
 
-template <typename T, typename W, bool LN> static int launch_norm_fwd_t(NormParams p, hipStream_t s) {
-    const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.w | (uintptr_t)p.b) & 15) == 0;
+template <typename T, typename W, bool LN, bool ADD = false> static int launch_norm_fwd_t(NormParams p, hipStream_t s) {
+    const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.w | (uintptr_t)p.b | (uintptr_t)p.r |
+                           (uintptr_t)p.h) & 15) == 0;
     bool done = false;
     if (aligned)
         done = dispatch_row_shape<T, 1>(p.emb, [&](auto shape) {
             constexpr int G = decltype(shape)::G, C = decltype(shape)::C;
             constexpr int RPB = G >= 256 ? 1 : 256 / G, NT = G > 256 ? G : 256;
             const long long grid = (p.n + RPB - 1) / RPB;
-            hipLaunchKernelGGL((norm_fwd_kernel<T, W, G, C, LN>), dim3((unsigned)grid), dim3(NT), 0, s, p);
+            hipLaunchKernelGGL((norm_fwd_kernel<T, W, G, C, LN, ADD>), dim3((unsigned)grid), dim3(NT), 0, s, p);
         });
-    if (!done) hipLaunchKernelGGL((norm_fwd_generic_kernel<T, W, LN>), dim3((unsigned)p.n), dim3(256), 0, s, p);
+    if (!done) hipLaunchKernelGGL((norm_fwd_generic_kernel<T, W, LN, ADD>), dim3((unsigned)p.n), dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
-// O: element type of dw / db (fp32 for RMSNorm, W for LayerNorm)
-template <typename T, typename W, typename O, bool LN>
+// O: element type of dw / db (fp32 for RMSNorm, W for LayerNorm).  ADD: p.r = dh, not NULL (a call without dh is the plain one)
+template <typename T, typename W, typename O, bool LN, bool ADD = false>
 static int launch_norm_bwd_t(NormParams p, void* dw, void* db, hipStream_t s) {
     const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.x | (uintptr_t)p.w | (uintptr_t)p.part_w |
-                           (uintptr_t)p.part_b) & 15) == 0;
+                           (uintptr_t)p.part_b | (uintptr_t)p.r) & 15) == 0;
     int parts = 0;
     bool done = false;
     if (aligned)
@@ -398,11 +480,11 @@ static int launch_norm_bwd_t(NormParams p, void* dw, void* db, hipStream_t s) {
             constexpr int RPB = G >= 256 ? 1 : 256 / G, NT = G > 256 ? G : 256;
             parts = norm_bwd_parts(p.n, p.emb, RPB);
             p.n_groups = parts * RPB;
-            hipLaunchKernelGGL((norm_bwd_kernel<T, W, G, C, LN>), dim3(parts), dim3(NT), 0, s, p);
+            hipLaunchKernelGGL((norm_bwd_kernel<T, W, G, C, LN, ADD>), dim3(parts), dim3(NT), 0, s, p);
         });
     if (!done) {
         parts = norm_bwd_parts(p.n, p.emb, 1);
-        hipLaunchKernelGGL((norm_bwd_generic_kernel<T, W, LN>), dim3(parts), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((norm_bwd_generic_kernel<T, W, LN, ADD>), dim3(parts), dim3(256), 0, s, p);
     }
     const unsigned fg = (unsigned)((p.emb + 31) / 32);
     hipLaunchKernelGGL((norm_fold_kernel<O>), dim3(fg, LN ? 2 : 1), dim3(1024), 0, s, (O*)dw, (O*)db,

@@ -12,6 +12,7 @@
 #   NNop.online_softmax(x) / NNop.∇online_softmax(Δ, y)       src/softmax.jl:60-80
 #   NNop._rms_norm / NNop.∇rms_norm                           src/rms_norm.jl:117-169
 #   NNop._layer_norm / NNop.∇layer_norm                       src/layer_norm.jl:150-204
+#   add_rms_norm / add_layer_norm (+ _fwd / _bwd, rrules)     the residual add fused into the norms (this library's own)
 #
 # `flash_attention` and the ChainRules `rrule` (src/attention_crc.jl:4-31) call these generically, so
 # `NNop.flash_attention(q, k, v; causal)` and `Zygote.gradient` keep working unchanged.
@@ -32,7 +33,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention, flash_attention_sinks, softcap_flash_attention
+export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -552,6 +553,100 @@ function NNop.∇layer_norm(Δ::ROCMatrix{T}, μ::ROCVector{Float32}, Σ::ROCVec
         (Ptr{NormDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
         d, devptr(dx), devptr(dw), devptr(db), devptr(Δ), devptr(μ), devptr(Σ), devptr(x), devptr(w), devptr(ws), nbytes, hipstream()))
     return dx, dw, db
+end
+
+
+# ---- residual add fused into the norms (include/nnop_hip.h: nnop_add_rms_norm and siblings; no counterpart in the reference) -----------
+# h = x + residual (one rounding to T) is written out and normalised in the same pass; the pullbacks take the cotangents of y and of h
+# and return ONE gradient, that of x and of residual alike.  `h_out` may be `x` or `residual` (in-place residual stream), `dx_out`
+# may be `dh`; the differentiable forms below never write in place.
+function add_rms_norm_fwd(x::ROCMatrix{T}, residual::ROCMatrix{T}, w::ROCVector{W}; ϵ::Float32 = 1f-6, offset::Float32 = 0f0,
+                          h_out::ROCMatrix{T} = similar(x)) where {T <: HipFloat, W <: HipFloat}
+    @assert size(x, 1) == length(w)
+    @assert size(residual) == size(x) && size(h_out) == size(x)
+    y = similar(x); rms = ROCArray{Float32}(undef, size(x, 2))
+    ok(GC.@preserve y h_out rms x residual w ccall((:nnop_add_rms_norm, libnnop()), Cint,
+        (Ptr{NormDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cfloat, Cfloat, Ptr{Cvoid}),
+        normdesc(x, w), devptr(y), devptr(h_out), devptr(rms), devptr(x), devptr(residual), devptr(w), offset, ϵ, hipstream()))
+    return y, h_out, rms
+end
+
+# dh: cotangent of h, or nothing (then exactly NNop.∇rms_norm on h)
+function add_rms_norm_bwd(Δ::ROCMatrix{T}, dh::Union{ROCMatrix{T}, Nothing}, rms::ROCVector{Float32}, h::ROCMatrix{T}, w::ROCVector{W};
+                          offset::Float32 = 0f0, dx_out::ROCMatrix{T} = similar(h)) where {T <: HipFloat, W <: HipFloat}
+    d = normdesc(h, w)
+    dw = ROCArray{Float32}(undef, size(h, 1))
+    nbytes = ccall((:nnop_norm_bwd_workspace_bytes, libnnop()), Csize_t, (Ptr{NormDesc}, Cint), d, 0)
+    ws = ROCArray{UInt8}(undef, nbytes)
+    ok(GC.@preserve dx_out dw Δ dh rms h w ws ccall((:nnop_add_rms_norm_bwd, libnnop()), Cint,
+        (Ptr{NormDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cfloat, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        d, devptr(dx_out), devptr(dw), devptr(Δ), devptr(dh), devptr(rms), devptr(h), devptr(w), offset, devptr(ws), nbytes, hipstream()))
+    return dx_out, dw
+end
+
+function add_layer_norm_fwd(x::ROCMatrix{T}, residual::ROCMatrix{T}, w::ROCVector{W}, b::ROCVector{W}; ϵ::Float32 = 1f-6,
+                            h_out::ROCMatrix{T} = similar(x)) where {T <: HipFloat, W <: HipFloat}
+    @assert size(x, 1) == length(w) == length(b)
+    @assert size(residual) == size(x) && size(h_out) == size(x)
+    y = similar(x); μ = ROCArray{Float32}(undef, size(x, 2)); Σ = similar(μ)
+    ok(GC.@preserve y h_out μ Σ x residual w b ccall((:nnop_add_layer_norm, libnnop()), Cint,
+        (Ptr{NormDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cfloat, Ptr{Cvoid}),
+        normdesc(x, w), devptr(y), devptr(h_out), devptr(μ), devptr(Σ), devptr(x), devptr(residual), devptr(w), devptr(b), ϵ, hipstream()))
+    return y, h_out, μ, Σ
+end
+
+function add_layer_norm_bwd(Δ::ROCMatrix{T}, dh::Union{ROCMatrix{T}, Nothing}, μ::ROCVector{Float32}, Σ::ROCVector{Float32},
+                            h::ROCMatrix{T}, w::ROCVector{W}; dx_out::ROCMatrix{T} = similar(h)) where {T <: HipFloat, W <: HipFloat}
+    d = normdesc(h, w)
+    dw = similar(w); db = similar(w)
+    nbytes = ccall((:nnop_norm_bwd_workspace_bytes, libnnop()), Csize_t, (Ptr{NormDesc}, Cint), d, 1)
+    ws = ROCArray{UInt8}(undef, nbytes)
+    ok(GC.@preserve dx_out dw db Δ dh μ Σ h w ws ccall((:nnop_add_layer_norm_bwd, libnnop()), Cint,
+        (Ptr{NormDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        d, devptr(dx_out), devptr(dw), devptr(db), devptr(Δ), devptr(dh), devptr(μ), devptr(Σ), devptr(h), devptr(w), devptr(ws), nbytes,
+        hipstream()))
+    return dx_out, dw, db
+end
+
+"""
+    add_rms_norm(x, residual, w; ϵ=1f-6, offset=0f0) -> (y, h)
+    add_layer_norm(x, residual, w, b; ϵ=1f-6) -> (y, h)
+
+`h = x + residual` and `y = rms_norm(h, w; ϵ, offset)` / `layer_norm(h, w, b; ϵ)` in one pass over memory (the pre-norm transformer block's
+add and norm).  Differentiable through the ChainRules rules below; the tangents of `x` and of `residual` are the same array.
+"""
+add_rms_norm(x, residual, w; ϵ::Float32 = 1f-6, offset::Float32 = 0f0) = add_rms_norm_fwd(x, residual, w; ϵ, offset)[1:2]
+add_layer_norm(x, residual, w, b; ϵ::Float32 = 1f-6) = add_layer_norm_fwd(x, residual, w, b; ϵ)[1:2]
+
+# a cotangent that is a ChainRules zero (an output the caller never used) reaches the library as a NULL pointer, not as zeros
+_cot(Δ, like) = Δ isa NNop.CRC.AbstractZero ? nothing : _to_roc(NNop.CRC.unthunk(Δ), like)
+
+function NNop.CRC.rrule(::typeof(add_rms_norm), x, residual, w; ϵ::Float32 = 1f-6, offset::Float32 = 0f0)
+    y, h, rms = add_rms_norm_fwd(x, residual, w; ϵ, offset)
+    function add_rms_norm_pullback(Δ)
+        dy, dh = _cot(Δ[1], y), _cot(Δ[2], h)
+        if isnothing(dy)                                  # only h was used: the add alone
+            dx = isnothing(dh) ? NNop.CRC.ZeroTangent() : dh
+            return NNop.CRC.NoTangent(), dx, dx, NNop.CRC.ZeroTangent()
+        end
+        dx, dw = add_rms_norm_bwd(dy, dh, rms, h, w; offset)
+        return NNop.CRC.NoTangent(), dx, dx, eltype(w) === Float32 ? dw : eltype(w).(dw)
+    end
+    return (y, h), add_rms_norm_pullback
+end
+
+function NNop.CRC.rrule(::typeof(add_layer_norm), x, residual, w, b; ϵ::Float32 = 1f-6)
+    y, h, μ, Σ = add_layer_norm_fwd(x, residual, w, b; ϵ)
+    function add_layer_norm_pullback(Δ)
+        dy, dh = _cot(Δ[1], y), _cot(Δ[2], h)
+        if isnothing(dy)
+            dx = isnothing(dh) ? NNop.CRC.ZeroTangent() : dh
+            return NNop.CRC.NoTangent(), dx, dx, NNop.CRC.ZeroTangent(), NNop.CRC.ZeroTangent()
+        end
+        dx, dw, db = add_layer_norm_bwd(dy, dh, μ, Σ, h, w)
+        return NNop.CRC.NoTangent(), dx, dx, dw, db
+    end
+    return (y, h), add_layer_norm_pullback
 end
 
 end # module

@@ -1,5 +1,7 @@
 """Bandwidth of the row-wise operators (online_softmax; later the norms) vs the HBM roofline.  Dev tool: one JSON line
-per shape.  usage: python tools/perf_rows.py [softmax] [--cpu]"""
+per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [--cpu]
+add_norms: the residual add fused into the norms against the two-call sequence it replaces, one JSON line per operator,
+direction and shape (profiles/add_norm/perf.jsonl is this mode's output)."""
 import json
 import os
 import sys
@@ -59,10 +61,13 @@ def softmax():
                               kind="port", cores=1, sample="N4096 batch4096 f32, median of 5")), flush=True)
 
 
+NORM_SHAPES = [(1024, 1024, "f32"), (4096, 16384, "bf16"), (4096, 16384, "f32"), (8192, 8192, "bf16"),
+               (768, 65536, "bf16"), (16384, 4096, "bf16"), (5120, 16384, "bf16")]
+
+
 def norms():
     norm_bytes = pkg.workmodel.norm_bytes
-    for emb, n, dt in [(1024, 1024, "f32"), (4096, 16384, "bf16"), (4096, 16384, "f32"), (8192, 8192, "bf16"),
-                       (768, 65536, "bf16"), (16384, 4096, "bf16"), (5120, 16384, "bf16")]:
+    for emb, n, dt in NORM_SHAPES:
         x = torch.randn(n, emb, device=DEV).to(DT[dt])
         dy = torch.randn(n, emb, device=DEV).to(DT[dt])
         w = torch.randn(emb, device=DEV); b = torch.randn(emb, device=DEV)
@@ -89,6 +94,77 @@ def norms():
                 t0 = time.perf_counter(); fn(); t.append(time.perf_counter() - t0)
             print(json.dumps(dict(op=name, cpu_baseline_gbps=round(norm_bytes(4096, 4096, 4) / np.median(t) / 1e9, 2),
                                   kind="port", cores=1, sample="emb4096 n4096 f32, median of 5")), flush=True)
+
+
+def _register_rows(emb, itemsize, bwd):
+    """does a row of emb elements take the register kernels (csrc/row_common.hpp: dispatch_row_shape / _narrow)?"""
+    if emb * itemsize % 16:
+        return False
+    chunks = emb * itemsize // 16
+    return chunks <= (1024 * (4 if itemsize == 4 else 2) if bwd else 1024 * 16)
+
+
+def add_norms():
+    """Per operator and direction: the fused call, the two-call sequence it replaces (forward: torch.add into a preallocated h, then
+    the plain norm; backward: the plain pullback, then torch.add of dh into dx) and the plain operator alone, each the median of 5
+    repeats of timeit() with the min-max spread.  gate: fused median below the sequence's median by more than the sequence's own
+    spread -- judged where the rows take the register kernels and x is at least 64 MiB, null elsewhere.  A missed gate ends the
+    run with a non-zero status after every line is printed."""
+    norm_bytes, add_norm_bytes = pkg.workmodel.norm_bytes, pkg.workmodel.add_norm_bytes
+
+    def med(fn):
+        t = sorted(timeit(fn) for _ in range(5))
+        return t[2], t[0], t[-1]
+
+    # --shape emb,n,dtype (repeatable): measure these shapes instead of the list
+    extra = [a.split("=", 1)[1].split(",") for a in sys.argv[1:] if a.startswith("--shape=")]
+    shapes = [(int(e), int(n), dt) for e, n, dt in extra] or NORM_SHAPES
+    failed = []
+    for emb, n, dt in shapes:
+        x = torch.randn(n, emb, device=DEV).to(DT[dt])
+        r, dy, dh = (torch.randn(n, emb, device=DEV).to(DT[dt]) for _ in range(3))
+        w = torch.randn(emb, device=DEV); b = torch.randn(emb, device=DEV)
+        h = torch.empty_like(x)
+        isz = x.element_size()
+        big = x.numel() * isz >= 64 * 2 ** 20
+        _, _, rms = pkg._add_rms_norm(x, r, w, h_out=h)
+        _, _, mu, sg = pkg._add_layer_norm(x, r, w, b, h_out=h)
+
+        def seq_rms_fwd():
+            torch.add(x, r, out=h)
+            return pkg._rms_norm(h, w)
+
+        def seq_ln_fwd():
+            torch.add(x, r, out=h)
+            return pkg._layer_norm(h, w, b)
+
+        def seq_rms_bwd():
+            dx, dw = pkg.grad_rms_norm(dy, rms, h, w)
+            return torch.add(dx, dh, out=dx), dw
+
+        def seq_ln_bwd():
+            dx, dw, db = pkg.grad_layer_norm(dy, mu, sg, h, w, b)
+            return torch.add(dx, dh, out=dx), dw, db
+
+        cases = [("add_rms_norm", False, lambda: pkg._add_rms_norm(x, r, w, h_out=h), seq_rms_fwd, lambda: pkg._rms_norm(h, w)),
+                 ("grad_add_rms_norm", True, lambda: pkg.grad_add_rms_norm(dy, dh, rms, h, w), seq_rms_bwd,
+                  lambda: pkg.grad_rms_norm(dy, rms, h, w)),
+                 ("add_layer_norm", False, lambda: pkg._add_layer_norm(x, r, w, b, h_out=h), seq_ln_fwd,
+                  lambda: pkg._layer_norm(h, w, b)),
+                 ("grad_add_layer_norm", True, lambda: pkg.grad_add_layer_norm(dy, dh, mu, sg, h, w, b), seq_ln_bwd,
+                  lambda: pkg.grad_layer_norm(dy, mu, sg, h, w, b))]
+        for op, bwd, fused, seq, plain in cases:
+            f, s, p = med(fused), med(seq), med(plain)
+            nb, nbp = add_norm_bytes(emb, n, isz, bwd=bwd), norm_bytes(emb, n, isz, bwd=bwd)
+            judged = big and _register_rows(emb, isz, bwd)
+            line(op, f"emb{emb} n{n}", dt, f[0], nb, us_min=round(f[1], 2), us_max=round(f[2], 2),
+                 seq_us=round(s[0], 2), seq_min=round(s[1], 2), seq_max=round(s[2], 2), ratio=round(f[0] / s[0], 3),
+                 plain_us=round(p[0], 2), plain_gbps=round(nbp / p[0] / 1e3, 1),
+                 gate=(bool(f[0] < s[0] - (s[2] - s[1])) if judged else None))
+            if judged and not f[0] < s[0] - (s[2] - s[1]):
+                failed.append(f"{op} emb{emb} n{n} {dt}")
+    if failed:
+        sys.exit("gate missed: " + "; ".join(failed))
 
 
 if __name__ == "__main__":
