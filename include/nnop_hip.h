@@ -69,7 +69,8 @@ typedef enum nnop_status {
                                       the element size for ms, ls.  Embedding dims that run the plain-HIP
                                       kernels (not 16 / 32 / 64 / 128 / 256) need element alignment only.      */
     NNOP_ERR_OPTS           = -12  /* invalid attention options (nnop_fa_opts): a reserved field is not 0, or a window
-                                      side is below -1 (ABI version 7)                                          */
+                                      side is below -1 (ABI version 7); nnop_glu_desc: an unknown act or layout, or
+                                      a bad alpha / limit                                                        */
 } nnop_status;
 
 /*
@@ -355,6 +356,60 @@ int nnop_add_layer_norm(const nnop_norm_desc* d, void* y, void* h, float* mu, fl
 int nnop_add_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* db, const void* dy,
                             const void* dh /* may be NULL */, const float* mu, const float* sigma, const void* h,
                             const void* w, void* workspace, size_t workspace_bytes, nnop_stream_t stream);
+
+/*
+ * Gated MLP activations (no counterpart in the reference): y = a(gate) * up, the element-wise step of a Llama / Gemma / gpt-oss MLP,
+ * forward and pullback in one pass over memory each (3 row-sized arrays moved forward instead of the two-op form's 5; 5 in the pullback
+ * instead of about 10).  fp32 arithmetic for every element type, one rounding on store.
+ *   NNOP_GLU_SILU        a(g) = g sigma(g)                                                  SwiGLU (Llama, Mistral, Qwen)
+ *   NNOP_GLU_GELU_TANH   a(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3)))              GeGLU (Gemma)
+ *   NNOP_GLU_GELU_ERF    a(g) = 0.5 g (1 + erf(g / sqrt 2))                                  GeGLU with the exact GELU
+ *   NNOP_GLU_SWIGLU_OAI  g' = min(g, limit), u' = clamp(u, -limit, limit), y = g' sigma(alpha g') (u' + 1)      gpt-oss (alpha = 1.702, limit = 7)
+ * Pullback: dgate = dy * up * a'(gate), dup = dy * a(gate); a and a' are recomputed from gate and up, nothing else is kept from the
+ * forward.  SWIGLU_OAI: the gradient passes through a clamp where the input is inside or ON the bound (torch's convention), and is 0
+ * outside; y and the gradients use u' + 1 and g'.  At large finite gates a and a' are finite and equal their limits (a = g, a' = 1 on
+ * the positive side; 0 and 0 on the negative side).
+ * Layouts (`ld` in elements):
+ *   NNOP_GLU_SPLIT        gate, up : [rows] rows of n elements, ld >= n apart, ONE ld for both.  Two dense matrices: ld = n.  The halves
+ *                         of a fused gate-up projection gu [rows][2n]: gate = gu, up = gu + n, ld = 2n -- no copy.  y, dy : dense [rows][n].
+ *                         dgate, dup : strided like gate, up; the elements between n and ld of a row are never written.
+ *   NNOP_GLU_INTERLEAVED  gate = gu[:, 0::2], up = gu[:, 1::2] of ONE array gu [rows][2n] (gpt-oss); ld must be 2n; `up` / `dup` must be NULL
+ *                         and `gate` / `dgate` are gu / dgu, dgu in the same layout.  y, dy : dense [rows][n].
+ * Aliasing that is allowed (element-wise safe; the same base address AND the same stride only): dgate may be gate, dup may be up, dgu may be
+ * gu; in the split forward y may be gate or up when ld == n.  ANY other overlap between an output and another argument is undefined.
+ * Every shape and alignment works: when all bases are 16-byte aligned and n and ld are multiples of 16 bytes' worth of elements the kernels
+ * move 16 bytes per access, otherwise single elements (slower, never an error).
+ * Checks, in this order, all before any device work: the descriptor -- NNOP_ERR_DTYPE; NNOP_ERR_OPTS for an unknown act or layout and, with
+ * SWIGLU_OAI only (the fields are ignored otherwise), an alpha that is not finite or a limit that is not finite and positive; NNOP_ERR_SHAPE
+ * for rows <= 0, n <= 0, reserved != 0, a split ld < n, an interleaved ld != 2n, or more work than one launch takes -- then NNOP_ERR_NULL for a
+ * NULL pointer (and for a non-NULL up / dup with the interleaved layout), then NNOP_ERR_ALIGN for a base not aligned to the element size.
+ * No workspace; asynchronous on the stream like every other entry point.
+ */
+typedef enum nnop_glu_act {
+    NNOP_GLU_SILU       = 0,
+    NNOP_GLU_GELU_TANH  = 1,
+    NNOP_GLU_GELU_ERF   = 2,
+    NNOP_GLU_SWIGLU_OAI = 3
+} nnop_glu_act;
+typedef enum nnop_glu_layout {
+    NNOP_GLU_SPLIT       = 0,
+    NNOP_GLU_INTERLEAVED = 1
+} nnop_glu_layout;
+typedef struct nnop_glu_desc {
+    int32_t dtype;     /* nnop_dtype of every array */
+    int32_t act;       /* nnop_glu_act */
+    int32_t layout;    /* nnop_glu_layout */
+    int32_t reserved;  /* must be 0 */
+    int64_t rows;
+    int64_t n;         /* row length of y (and of gate, up) */
+    int64_t ld;        /* row stride of gate, up, dgate, dup in elements; interleaved: 2n */
+    float   alpha;     /* SWIGLU_OAI only */
+    float   limit;     /* SWIGLU_OAI only */
+} nnop_glu_desc;
+
+int nnop_glu(const nnop_glu_desc* d, void* y, const void* gate, const void* up /* NULL iff interleaved */, nnop_stream_t stream);
+int nnop_glu_bwd(const nnop_glu_desc* d, void* dgate, void* dup /* NULL iff interleaved */, const void* dy,
+                 const void* gate, const void* up /* NULL iff interleaved */, nnop_stream_t stream);
 
 /*
  * Sharding over several devices (ABI version 6).  The reference has no multi-GPU code; its (batch, kv-head) slices -- a KV head with its

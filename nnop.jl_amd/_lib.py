@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = (
     "nnop_add_rms_norm_bwd",
     "nnop_add_layer_norm",
     "nnop_add_layer_norm_bwd",
+    "nnop_glu",
+    "nnop_glu_bwd",
     "nnop_fa_shards",
     "nnop_shared_memory",
     "nnop_strerror",
@@ -115,6 +117,17 @@ class NormDesc(C.Structure):
     """struct nnop_norm_desc"""
     _fields_ = [("dtype", C.c_int32), ("w_dtype", C.c_int32), ("emb", C.c_int32), ("reserved", C.c_int32),
                 ("n", C.c_int64)]
+
+
+# nnop_glu_act / nnop_glu_layout (include/nnop_hip.h)
+GLU_ACTS = {"silu": 0, "gelu_tanh": 1, "gelu_erf": 2, "swiglu_oai": 3}
+GLU_SPLIT, GLU_INTERLEAVED = 0, 1
+
+
+class GluDesc(C.Structure):
+    """struct nnop_glu_desc"""
+    _fields_ = [("dtype", C.c_int32), ("act", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("n", C.c_int64), ("ld", C.c_int64), ("alpha", C.c_float), ("limit", C.c_float)]
 
 
 class NNopLibraryMissing(ImportError):
@@ -193,6 +206,11 @@ def load():
     lib.nnop_add_layer_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]
     lib.nnop_add_layer_norm_bwd.restype = C.c_int
     lib.nnop_add_layer_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    gd = C.POINTER(GluDesc)
+    lib.nnop_glu.restype = C.c_int
+    lib.nnop_glu.argtypes = [gd, vp, vp, vp, vp]
+    lib.nnop_glu_bwd.restype = C.c_int
+    lib.nnop_glu_bwd.argtypes = [gd, vp, vp, vp, vp, vp, vp]
     lib.nnop_fa_shards.restype = C.c_int
     lib.nnop_fa_shards.argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int, C.POINTER(FaShard)]
     lib.nnop_shared_memory.restype = C.c_int

@@ -94,6 +94,11 @@ int launch_add_layer_norm_bwd(const nnop_norm_desc& d, void* dx, void* dw, void*
                               const float* mu, const float* sigma, const void* h, const void* w, void* ws, hipStream_t s);
 size_t norm_ws_bytes(const nnop_norm_desc& d, bool ln);
 
+// glu.hip (interleaved layout: gate = gu, dgate = dgu, up = dup = nullptr)
+int launch_glu(const nnop_glu_desc& d, void* y, const void* gate, const void* up, hipStream_t s);
+int launch_glu_bwd(const nnop_glu_desc& d, void* dgate, void* dup, const void* dy, const void* gate, const void* up,
+                   hipStream_t s);
+
 // Embedding dims the MFMA kernels are instantiated for.
 // MFMA-tiled kernels: 16, 32, 64, 128; every other power of two up to 512: fa_generic.hpp (correctness path)
 inline bool emb_tiled(int e) { return e == 16 || e == 32 || e == 64 || e == 128; }

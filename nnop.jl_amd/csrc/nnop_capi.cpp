@@ -144,9 +144,11 @@ const char* nnop_strerror(int status) {
         case NNOP_ERR_WORKSPACE: return "Backward workspace is smaller than nnop_*_bwd_workspace_bytes().";
         case NNOP_ERR_HIP: return "HIP runtime error at kernel launch.";
         case NNOP_ERR_ALIGN:
-            return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls).";
+            return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls "
+                   "and for the arrays of nnop_glu).";
         case NNOP_ERR_OPTS:
-            return "Invalid attention options (a reserved field is not 0, a window side is below -1, or a soft cap is negative or not finite).";
+            return "Invalid options (attention: a reserved field is not 0, a window side is below -1, or a soft cap is negative or not finite; "
+                   "nnop_glu: an unknown act or layout, or with swiglu_oai an alpha that is not finite or a limit that is not finite and positive).";
         default: return "unknown nnop status";
     }
 }
@@ -351,6 +353,49 @@ int nnop_add_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* d
     if (!dx || !dw || !db || !dy || !mu || !sigma || !h || !w || !workspace) return NNOP_ERR_NULL;   // dh may be NULL
     if (workspace_bytes < norm_ws_bytes(*d, true)) return NNOP_ERR_WORKSPACE;
     return launch_add_layer_norm_bwd(*d, dx, dw, db, dy, dh, mu, sigma, h, w, workspace, (hipStream_t)stream);
+}
+
+// descriptor, then pointers, then alignment; `ptrs`: the arguments that must be non-NULL, `absent`: those that the interleaved
+// layout forbids (up, dup)
+static int check_glu(const nnop_glu_desc* d, const void* const* ptrs, int n_ptrs, const void* const* absent, int n_absent) {
+    if (!d) return NNOP_ERR_NULL;
+    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (d->act < NNOP_GLU_SILU || d->act > NNOP_GLU_SWIGLU_OAI) return NNOP_ERR_OPTS;
+    if (d->layout != NNOP_GLU_SPLIT && d->layout != NNOP_GLU_INTERLEAVED) return NNOP_ERR_OPTS;
+    if (d->act == NNOP_GLU_SWIGLU_OAI) {                                                       // (the comparisons are false for NaN)
+        if (!(d->alpha >= -3.4028234664e38f && d->alpha <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
+        if (!(d->limit > 0.f && d->limit <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
+    }
+    if (d->rows <= 0 || d->n <= 0 || d->reserved != 0) return NNOP_ERR_SHAPE;
+    const bool il = d->layout == NNOP_GLU_INTERLEAVED;
+    if (il ? (d->n > LLONG_MAX / 2 || d->ld != 2 * d->n) : d->ld < d->n) return NNOP_ERR_SHAPE;
+    for (int i = 0; i < n_ptrs; ++i)
+        if (!ptrs[i]) return NNOP_ERR_NULL;
+    for (int i = 0; i < n_absent; ++i)
+        if (il ? absent[i] != nullptr : absent[i] == nullptr) return NNOP_ERR_NULL;
+    const size_t ea = d->dtype == NNOP_F32 ? 4 : 2;
+    for (int i = 0; i < n_ptrs; ++i)
+        if (misaligned(ptrs[i], ea)) return NNOP_ERR_ALIGN;
+    for (int i = 0; i < n_absent; ++i)
+        if (misaligned(absent[i], ea)) return NNOP_ERR_ALIGN;
+    return NNOP_OK;
+}
+
+int nnop_glu(const nnop_glu_desc* d, void* y, const void* gate, const void* up, nnop_stream_t stream) {
+    const void* const ptrs[] = {y, gate};
+    const void* const absent[] = {up};
+    const int st = check_glu(d, ptrs, 2, absent, 1);
+    if (st != NNOP_OK) return st;
+    return launch_glu(*d, y, gate, up, (hipStream_t)stream);
+}
+
+int nnop_glu_bwd(const nnop_glu_desc* d, void* dgate, void* dup, const void* dy, const void* gate, const void* up,
+                 nnop_stream_t stream) {
+    const void* const ptrs[] = {dgate, dy, gate};
+    const void* const absent[] = {dup, up};
+    const int st = check_glu(d, ptrs, 3, absent, 2);
+    if (st != NNOP_OK) return st;
+    return launch_glu_bwd(*d, dgate, dup, dy, gate, up, (hipStream_t)stream);
 }
 
 size_t nnop_norm_bwd_workspace_bytes(const nnop_norm_desc* d, int layer_norm) {

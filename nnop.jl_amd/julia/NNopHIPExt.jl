@@ -13,6 +13,7 @@
 #   NNop._rms_norm / NNop.∇rms_norm                           src/rms_norm.jl:117-169
 #   NNop._layer_norm / NNop.∇layer_norm                       src/layer_norm.jl:150-204
 #   add_rms_norm / add_layer_norm (+ _fwd / _bwd, rrules)     the residual add fused into the norms (this library's own)
+#   glu (+ glu_fwd / glu_bwd, rrules)                         gated MLP activations: SwiGLU, GeGLU, gpt-oss (this library's own)
 #
 # `flash_attention` and the ChainRules `rrule` (src/attention_crc.jl:4-31) call these generically, so
 # `NNop.flash_attention(q, k, v; causal)` and `Zygote.gradient` keep working unchanged.
@@ -33,7 +34,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm
+export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm, glu
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -647,6 +648,99 @@ function NNop.CRC.rrule(::typeof(add_layer_norm), x, residual, w, b; ϵ::Float32
         return NNop.CRC.NoTangent(), dx, dx, dw, db
     end
     return (y, h), add_layer_norm_pullback
+end
+
+
+# ---- gated MLP activations (include/nnop_hip.h: nnop_glu / nnop_glu_bwd; no counterpart in the reference) -----------------------------
+# y = act(gate) .* up in one pass; the pullback recomputes act and its derivative from gate and up.  Matrices are (n, rows) -- the same
+# memory as the header's [rows][n].  `gate` and `up` may be two dense matrices or the two halves `view(gu, 1:n, :)`, `view(gu, n+1:2n, :)`
+# of one fused projection (one common column stride `ld`, no copy); `glu(gu; layout = :interleaved)` takes gate = gu[1:2:end, :],
+# up = gu[2:2:end, :] (gpt-oss).
+struct GluDesc
+    dtype::Int32; act::Int32; layout::Int32; reserved::Int32
+    rows::Int64; n::Int64; ld::Int64
+    alpha::Float32; limit::Float32
+end
+const GLU_ACTS = (silu = Int32(0), gelu_tanh = Int32(1), gelu_erf = Int32(2), swiglu_oai = Int32(3))
+const RowsOf{T} = Union{ROCMatrix{T}, SubArray{T, 2, <:ROCMatrix{T}, <:Tuple{UnitRange{Int}, Base.Slice}}}
+_ld(x) = stride(x, 2)
+gludesc(x, act::Symbol, layout, n, ld, alpha, limit) =
+    Ref(GluDesc(nnop_dtype(eltype(x)), GLU_ACTS[act], layout, 0, size(x, 2), n, ld, alpha, limit))
+
+function glu_fwd(gate::RowsOf{T}, up::RowsOf{T}; act::Symbol = :silu, alpha::Float32 = 1.702f0, limit::Float32 = 7f0,
+                 y::ROCMatrix{T} = ROCArray{T}(undef, size(gate))) where {T <: HipFloat}
+    @assert size(gate) == size(up) == size(y) && _ld(gate) == _ld(up)
+    d = gludesc(gate, act, 0, size(gate, 1), size(gate, 2) == 1 ? size(gate, 1) : _ld(gate), alpha, limit)
+    ok(GC.@preserve y gate up ccall((:nnop_glu, libnnop()), Cint,
+        (Ptr{GluDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(y), devptr(gate), devptr(up), hipstream()))
+    return y
+end
+
+# dgate / dup: laid out like gate / up (they may BE gate / up: in place)
+function glu_bwd(Δ::ROCMatrix{T}, gate::RowsOf{T}, up::RowsOf{T}; act::Symbol = :silu, alpha::Float32 = 1.702f0, limit::Float32 = 7f0,
+                 dgate::RowsOf{T} = ROCArray{T}(undef, size(gate)), dup::RowsOf{T} = ROCArray{T}(undef, size(up))) where {T <: HipFloat}
+    @assert size(gate) == size(up) == size(Δ) && _ld(gate) == _ld(up)
+    if _ld(dgate) != _ld(gate) || _ld(dup) != _ld(gate)      # fresh dense gradients for strided inputs: dense copies of the inputs
+        gate, up = ROCArray(gate), ROCArray(up)
+    end
+    d = gludesc(gate, act, 0, size(gate, 1), size(gate, 2) == 1 ? size(gate, 1) : _ld(gate), alpha, limit)
+    ok(GC.@preserve dgate dup Δ gate up ccall((:nnop_glu_bwd, libnnop()), Cint,
+        (Ptr{GluDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(dgate), devptr(dup), devptr(Δ), devptr(gate), devptr(up), hipstream()))
+    return dgate, dup
+end
+
+# one fused projection gu (2n, rows)
+function glu_fwd(gu::ROCMatrix{T}; layout::Symbol = :halves, kw...) where {T <: HipFloat}
+    n = size(gu, 1) ÷ 2
+    @assert size(gu, 1) == 2n && layout in (:halves, :interleaved)
+    layout === :halves && return glu_fwd(view(gu, 1:n, :), view(gu, n+1:2n, :); kw...)
+    act = get(kw, :act, :silu); alpha = get(kw, :alpha, 1.702f0); limit = get(kw, :limit, 7f0)
+    y = ROCArray{T}(undef, n, size(gu, 2))
+    d = gludesc(gu, act, 1, n, 2n, alpha, limit)
+    ok(GC.@preserve y gu ccall((:nnop_glu, libnnop()), Cint,
+        (Ptr{GluDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(y), devptr(gu), devptr(nothing), hipstream()))
+    return y
+end
+
+function glu_bwd(Δ::ROCMatrix{T}, gu::ROCMatrix{T}; layout::Symbol = :halves, dgu::ROCMatrix{T} = similar(gu), kw...) where {T <: HipFloat}
+    n = size(gu, 1) ÷ 2
+    @assert size(gu, 1) == 2n && size(Δ) == (n, size(gu, 2)) && size(dgu) == size(gu)
+    if layout === :halves
+        glu_bwd(Δ, view(gu, 1:n, :), view(gu, n+1:2n, :); dgate = view(dgu, 1:n, :), dup = view(dgu, n+1:2n, :), kw...)
+        return dgu
+    end
+    act = get(kw, :act, :silu); alpha = get(kw, :alpha, 1.702f0); limit = get(kw, :limit, 7f0)
+    d = gludesc(gu, act, 1, n, 2n, alpha, limit)
+    ok(GC.@preserve dgu Δ gu ccall((:nnop_glu_bwd, libnnop()), Cint,
+        (Ptr{GluDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(dgu), devptr(nothing), devptr(Δ), devptr(gu), devptr(nothing), hipstream()))
+    return dgu
+end
+
+"""
+    glu(gate, up; act=:silu, alpha=1.702f0, limit=7f0) -> y
+    glu(gu; layout=:halves, act=:silu, ...) -> y
+
+`y = act(gate) .* up`: SwiGLU (`:silu`), GeGLU (`:gelu_tanh`, `:gelu_erf`) and the clamped gpt-oss SwiGLU (`:swiglu_oai`,
+`min(g, limit) * σ(alpha * min(g, limit)) * (clamp(u, -limit, limit) + 1)`).  Differentiable through the ChainRules rules below, which keep
+only `gate` and `up` (or `gu`).
+"""
+glu(gate, up; kw...) = glu_fwd(gate, up; kw...)
+glu(gu; kw...) = glu_fwd(gu; kw...)
+
+function NNop.CRC.rrule(::typeof(glu), gate, up; kw...)
+    y = glu_fwd(gate, up; kw...)
+    glu_pullback(Δ) = (NNop.CRC.NoTangent(), glu_bwd(_to_roc(NNop.CRC.unthunk(Δ), y), gate, up; kw...)...)
+    return y, glu_pullback
+end
+
+function NNop.CRC.rrule(::typeof(glu), gu; kw...)
+    y = glu_fwd(gu; kw...)
+    glu_packed_pullback(Δ) = (NNop.CRC.NoTangent(), glu_bwd(_to_roc(NNop.CRC.unthunk(Δ), y), gu; kw...))
+    return y, glu_packed_pullback
 end
 
 end # module

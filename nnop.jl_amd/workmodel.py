@@ -2,7 +2,7 @@
 measured time.  Pure arithmetic on shapes; part of the product so that measurement code never needs the test oracle."""
 from __future__ import annotations
 
-__all__ = ["attention_flops", "attention_bytes", "rope_bytes", "softmax_bytes", "norm_bytes", "add_norm_bytes"]
+__all__ = ["attention_flops", "attention_bytes", "rope_bytes", "softmax_bytes", "norm_bytes", "add_norm_bytes", "glu_bytes"]
 
 
 def attention_flops(E, QL, KL, QH, B, *, causal: bool, mode: str = "fwd", kv_lens=None):
@@ -47,3 +47,8 @@ def add_norm_bytes(emb, n, itemsize, bwd=False):
     """residual add fused into the norm: forward reads x, residual and writes h, y; pullback (with dh) reads dy, h, dh and
     writes dx -- four row-sized arrays either way."""
     return 4 * emb * n * itemsize
+
+
+def glu_bytes(n, rows, itemsize, bwd=False):
+    """gated activation y = act(gate) * up: forward reads gate, up and writes y; pullback reads dy, gate, up and writes dgate, dup."""
+    return (5 if bwd else 3) * n * rows * itemsize

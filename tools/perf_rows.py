@@ -1,7 +1,8 @@
 """Bandwidth of the row-wise operators (online_softmax; later the norms) vs the HBM roofline.  Dev tool: one JSON line
-per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [--cpu]
+per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [glu [--shape=rows,n,dtype,layout ...]] [--cpu]
 add_norms: the residual add fused into the norms against the two-call sequence it replaces, one JSON line per operator,
-direction and shape (profiles/add_norm/perf.jsonl is this mode's output)."""
+direction and shape (profiles/add_norm/perf.jsonl is this mode's output).
+glu: the gated MLP activations against the torch sequence they replace (profiles/glu/perf.jsonl)."""
 import json
 import os
 import sys
@@ -165,6 +166,99 @@ def add_norms():
                 failed.append(f"{op} emb{emb} n{n} {dt}")
     if failed:
         sys.exit("gate missed: " + "; ".join(failed))
+
+
+GLU_SHAPES = [(8192, 14336, "bf16", "split"), (4096, 28672, "bf16", "split"), (32768, 2880, "bf16", "interleaved"),
+              (8192, 14336, "f32", "split"), (1024, 1024, "bf16", "split"), (8192, 14336, "bf16", "halves")]
+
+
+def _glu_torch(g, u, act, alpha=1.702, limit=7.0):
+    """the torch sequence a model runs without the fused call"""
+    F = torch.nn.functional
+    if act == "silu":
+        return F.silu(g) * u
+    if act == "gelu_tanh":
+        return F.gelu(g, approximate="tanh") * u
+    if act == "gelu_erf":
+        return F.gelu(g, approximate="none") * u
+    g = g.clamp(min=None, max=limit)                 # gpt-oss
+    u = u.clamp(min=-limit, max=limit)
+    glu = g * torch.sigmoid(g * alpha)
+    return (u + 1) * glu
+
+
+def glu():
+    """Gated activations against the torch sequence they replace: per shape, activation and direction the fused call and the
+    sequence (forward: the formula; backward: autograd of it, graph kept, backward alone timed), alternating in one process,
+    5 repeats of timeit() each: median with the min-max spread, algorithmic GB/s from workmodel.glu_bytes, ratio of the medians.
+    Interleaved shapes: the sequence reads gu[:, 0::2] and gu[:, 1::2]; "halves": both sides read gu.chunk(2, -1) (ld = 2n).  --out=FILE (default profiles/glu/perf.jsonl) also gets
+    the lines; --tag=NAME labels them (a library variant under NNOP_LIB_PATH).  A large shape (>= 64 MiB per array) where the
+    fused call is slower than the sequence ends the run with a non-zero status after every line is printed."""
+    glu_bytes = pkg.workmodel.glu_bytes
+    out = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")] or [os.path.join(ROOT, "profiles", "glu", "perf.jsonl")])[0]
+    tag = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--tag=")] or [None])[0]
+    extra = [a.split("=", 1)[1].split(",") for a in sys.argv[1:] if a.startswith("--shape=")]
+    shapes = [(int(r), int(n), dt, lay) for r, n, dt, lay in extra] or GLU_SHAPES
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    failed, lines = [], []
+    for rows, n, dt, layout in shapes:
+        il = layout == "interleaved"
+        isz = torch.empty(0, dtype=DT[dt]).element_size()
+        big = rows * n * isz >= 64 * 2 ** 20
+        if il:
+            gu = (3 * torch.randn(rows, 2 * n, device=DEV)).to(DT[dt])
+            g, u = gu[:, 0::2], gu[:, 1::2]
+        elif layout == "halves":                         # split addressing with ld = 2n: the chunk views of one projection
+            gu = (3 * torch.randn(rows, 2 * n, device=DEV)).to(DT[dt])
+            g, u = gu.chunk(2, -1)
+        else:
+            g, u = ((3 * torch.randn(rows, n, device=DEV)).to(DT[dt]) for _ in range(2))
+        dy = torch.randn(rows, n, device=DEV).to(DT[dt])
+        y = torch.empty_like(dy)
+        for act in ("silu", "gelu_tanh", "gelu_erf", "swiglu_oai"):
+            if il:
+                dgu = torch.empty_like(gu)
+                fused_f = lambda: pkg.glu_packed(gu, act=act, layout="interleaved")
+                fused_b = lambda: pkg.grad_glu_packed(dy, gu, act=act, layout="interleaved", dgu_out=dgu)
+                leaf = gu.clone().requires_grad_(True)
+                yt = _glu_torch(leaf[:, 0::2], leaf[:, 1::2], act)
+                seq_b = lambda: torch.autograd.grad(yt, (leaf,), dy, retain_graph=True)
+            else:
+                if layout == "halves":
+                    dg, du = torch.empty_like(gu).chunk(2, -1)
+                    leaf = gu.clone().requires_grad_(True)
+                    yt = _glu_torch(*leaf.chunk(2, -1), act)
+                    seq_b = lambda: torch.autograd.grad(yt, (leaf,), dy, retain_graph=True)
+                else:
+                    dg, du = torch.empty_like(g), torch.empty_like(u)
+                    lg, lu = g.clone().requires_grad_(True), u.clone().requires_grad_(True)
+                    yt = _glu_torch(lg, lu, act)
+                    seq_b = lambda: torch.autograd.grad(yt, (lg, lu), dy, retain_graph=True)
+                fused_f = lambda: pkg.glu_into(y, g, u, act=act)
+                fused_b = lambda: pkg.grad_glu_into(dg, du, dy, g, u, act=act)
+            seq_f = lambda: _glu_torch(g, u, act)
+            for op, bwd, fused, seq in ((f"glu[{act}]", False, fused_f, seq_f), (f"grad_glu[{act}]", True, fused_b, seq_b)):
+                tf, ts = [], []
+                for _ in range(5):                       # alternate: fused, sequence, fused, ...
+                    tf.append(timeit(fused))
+                    ts.append(timeit(seq))
+                tf.sort(); ts.sort()
+                nb = glu_bytes(n, rows, isz, bwd=bwd)
+                d = dict(op=op, shape=f"rows{rows} n{n}", layout=layout, dtype=dt, us=round(tf[2], 2), us_min=round(tf[0], 2),
+                         us_max=round(tf[4], 2), bytes=nb, tbps=round(nb / tf[2] / 1e6, 3), seq_us=round(ts[2], 2),
+                         seq_min=round(ts[0], 2), seq_max=round(ts[4], 2), ratio=round(tf[2] / ts[2], 3),
+                         gate=(bool(tf[2] <= ts[2]) if big else None))
+                if tag:
+                    d["tag"] = tag
+                print(json.dumps(d), flush=True)
+                lines.append(json.dumps(d))
+                if big and not tf[2] <= ts[2]:
+                    failed.append(f"{op} rows{rows} n{n} {dt}")
+            del yt
+        with open(out, "w") as f:                        # rewritten after every shape: a run that is cut short keeps what it has
+            f.write("\n".join(lines) + "\n")
+    if failed:
+        sys.exit("fused slower than the torch sequence: " + "; ".join(failed))
 
 
 if __name__ == "__main__":
