@@ -71,7 +71,7 @@ EXPORTED_SYMBOLS = (
 DEBUG_SYMBOLS = ("nnop_debug_set", "nnop_debug_dev_build", "nnop_debug_fwd_form", "nnop_debug_bwd_form",
                  "nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex", "nnop_debug_fwd_form_cap", "nnop_debug_bwd_form_cap")
 FWD_FORMS = {0: "fa_fwd_kernel", 1: "fa_fwd_split_kernel", 2: "fa_fwd_w64_kernel", 3: "fa_fwd_generic_kernel", 4: "fa_fwd_duo_kernel"}
-FWD_FORMS_CAP = {0: "fa_fwd_cap_kernel", 3: "fa_fwd_generic_cap_kernel"}      # a capped call runs these two forms only
+FWD_FORMS_CAP = {0: "fa_fwd_cap_kernel", 3: "fa_fwd_generic_cap_kernel"}      # a capped call runs these two forms only; form names, not symbols (fwd_form)
 # keys of nnop_debug_set == enum TuneKey (csrc/tuning.hpp)
 TUNE_KEYS = {"fwd_split": 0, "fwd_nw": 1, "fwd_w64": 2, "bwd_big7": 3, "norm_bwd_cap": 4, "bwd_nw": 5,
              "fwd_exact_scale": 6, "bwd_w64": 7, "bwd_stages": 8, "fwd_persist": 9, "bwd_persist": 10, "fwd_duo": 11, "fwd_persist_asc": 12, "bwd_narrow": 13, "fwd_causal_alt": 14}
@@ -299,8 +299,9 @@ def fa_softcap(softcap=None):
 
 
 def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None, softcap=None) -> str:
-    """Name of the forward kernel the launcher picks for this problem (reporting only; csrc/nnop_debug.h).  It names the form: a
-    call with sinks launches the form's `_sink_kernel` twin (fa_fwd_sink_kernel, fa_fwd_cap_sink_kernel, ...)."""
+    """Name of the forward kernel the launcher picks for this problem (reporting only; csrc/nnop_debug.h).  It names the form, not
+    the symbol: a capped call launches the CAP = true instantiation of fa_fwd_kernel / fa_fwd_generic_kernel, a call with sinks the
+    SINK = true instantiation of the form's kernel."""
     opts = fa_opts(window)
     if fa_softcap(softcap) != 0.0:
         code = load().nnop_debug_fwd_form_cap(C.byref(desc), C.byref(opts) if opts is not None else None, fa_softcap(softcap),
@@ -319,7 +320,7 @@ def fwd_form(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, windo
 def bwd_kernels(desc: FaDesc, has_pair: bool = False, has_mask: bool = False, window=None, softcap=None):
     """Names of the (dK/dV, dQ) kernels the launcher picks for this problem (reporting only; csrc/nnop_debug.h).  It tells the w64
     backward from the fa_bwd.hpp one and no more: the plain-HIP kernels (fa_bwd_generic_*) report as the latter, and a capped call
-    launches the same templates with the cap bit of MODE set (MODE 5, 6) or the plain-HIP `_cap_kernel` twins."""
+    launches the same templates with the cap bit of MODE set (MODE 5, 6) or the CAP = true instantiations of the plain-HIP kernels."""
     opts = fa_opts(window)
     if fa_softcap(softcap) != 0.0:
         code = load().nnop_debug_bwd_form_cap(C.byref(desc), C.byref(opts) if opts is not None else None, fa_softcap(softcap),

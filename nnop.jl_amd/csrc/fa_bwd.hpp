@@ -68,7 +68,7 @@ struct BwdParams {
     int   persist = 0;   // fa_bwd_w64_kernel: blocks per workgroup of the persistent form (grid = 256 workgroups), 0 = one block per workgroup
     int   win_left = -1;    // the WIN = true kernels and the plain-HIP ones: sliding window (FaWindow, normalised), -1 = unbounded side
     int   win_right = -1;   // (behind the older fields: their kernel-argument offsets stay where they were)
-    float cap_ka = 0.f;     // the soft-capped kernels (MODE | kBwdCap, fa_bwd_generic_*_cap_kernel): the folded constants of SoftcapK
+    float cap_ka = 0.f;     // the soft-capped kernels (MODE | kBwdCap, fa_bwd_generic_*_kernel<T, CAP = true>): the folded constants of SoftcapK
     float cap_kb = 0.f;     // (fa_launch.hpp), behind the window for the same reason
 };
 

@@ -329,13 +329,9 @@ template <typename T> static int launch_bwd_generic(const nnop_fa_desc& d, const
         if (hipMemsetAsync(p.dpair, 0, bytes, s) != hipSuccess) { (void)hipGetLastError(); return NNOP_ERR_HIP; }
     }
     hipLaunchKernelGGL((fa_bwd_generic_pre_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-    if (a.softcap != 0.f) {
-        hipLaunchKernelGGL((fa_bwd_generic_dq_cap_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-        hipLaunchKernelGGL((fa_bwd_generic_dkdv_cap_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
-    } else {
-        hipLaunchKernelGGL((fa_bwd_generic_dq_kernel<T>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
-        hipLaunchKernelGGL((fa_bwd_generic_dkdv_kernel<T>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
-    }
+    const bool cap = a.softcap != 0.f;
+    hipLaunchKernelGGL((cap ? fa_bwd_generic_dq_kernel<T, true> : fa_bwd_generic_dq_kernel<T, false>), dim3((unsigned)gq), dim3(256), 0, s, p, d.emb, n_rows);
+    hipLaunchKernelGGL((cap ? fa_bwd_generic_dkdv_kernel<T, true> : fa_bwd_generic_dkdv_kernel<T, false>), dim3((unsigned)gk), dim3(256), 0, s, p, d.emb, n_krows);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 

@@ -98,8 +98,8 @@ struct FwdParams {
     // the SINK = true instantiations of every form: learned per-head attention sinks, fp32 [QH], merged in the epilogue (sink_merge).
     // Behind the window for the same reason.
     const float* sinks = nullptr;
-    // the CAP = true instantiations (fa_fwd_cap_kernel, fa_fwd_cap_sink_kernel) and fa_fwd_generic_cap_*: logit soft-capping, the two
-    // folded constants of SoftcapK (fa_launch.hpp).  Behind the sinks for the same reason.
+    // the CAP = true instantiations of fa_fwd_kernel and fa_fwd_generic_kernel: logit soft-capping, the two folded constants of
+    // SoftcapK (fa_launch.hpp).  Behind the sinks for the same reason.
     float cap_ka = 0.f;
     float cap_kb = 0.f;
 #ifdef NNOP_DEV_BUILD
@@ -114,36 +114,11 @@ struct FwdParams {
 // are RELATIVE to t_lo (tile t of the walk is kv tile t0 + t), each wave computes only its own live tiles [w_lo, n_live), one
 // tile per interval (no software pipeline, see kPipe), and takes the per-element select only on tiles that cross a window
 // edge, the diagonal, KL or a key-padding word (tile_needs_mask).  WIN = false compiles to the code without a window.
-// SINK: learned attention sinks (p.sinks, non-null), merged in the epilogue.  One text, fa_fwd_kernel.inc, two kernels: fa_fwd_kernel
-// (SINK = false: the sink code compiles away) for the calls without sinks, fa_fwd_sink_kernel for the calls with them.
+// SINK: learned attention sinks (p.sinks, non-null), merged in the epilogue.  SINK = false (the calls without sinks) compiles the sink
+// code away.
 // CAP (MODE 1 / 2 only, instantiated with WIN = true only): logit soft-capping, x = c * tanh(s * scale / c) (+ pair), applied in finish_x
-// to the raw accumulators; the tile is then in log2 units, as with a pair bias.  Two more kernels of the same text, fa_fwd_cap_kernel
-// and fa_fwd_cap_sink_kernel: the kernels of the calls without a cap keep their names and their code.
-#define NNOP_FWD_NAME fa_fwd_kernel
-#define NNOP_FWD_SINK false
-#define NNOP_FWD_CAP false
+// to the raw accumulators; the tile is then in log2 units, as with a pair bias.  CAP = false (the calls without a cap) compiles it away.
 #include "fa_fwd_kernel.inc"
-#undef NNOP_FWD_NAME
-#undef NNOP_FWD_SINK
-#define NNOP_FWD_NAME fa_fwd_sink_kernel
-#define NNOP_FWD_SINK true
-#include "fa_fwd_kernel.inc"
-#undef NNOP_FWD_NAME
-#undef NNOP_FWD_SINK
-#undef NNOP_FWD_CAP
-#define NNOP_FWD_CAP true
-#define NNOP_FWD_NAME fa_fwd_cap_kernel
-#define NNOP_FWD_SINK false
-#include "fa_fwd_kernel.inc"
-#undef NNOP_FWD_NAME
-#undef NNOP_FWD_SINK
-#define NNOP_FWD_NAME fa_fwd_cap_sink_kernel
-#define NNOP_FWD_SINK true
-#include "fa_fwd_kernel.inc"
-#undef NNOP_FWD_NAME
-#undef NNOP_FWD_SINK
-#undef NNOP_FWD_CAP
-
 
 // LDS bytes the kernel needs: K ring of 2 + V ring of 2 + one scratch slot + (key padding) one 64-bit validity
 // word per kv tile for up to kMaxMaskTiles tiles (longer sequences fall back to reading the mask per tile).

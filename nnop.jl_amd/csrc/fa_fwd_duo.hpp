@@ -142,16 +142,6 @@ template <typename T, int E> constexpr int fa_fwd_duo_lds_bytes(bool masked) {
 // half left out -- 32 rows per wave, 128 per workgroup, for problems whose 256-row blocks cannot fill the chip (twice the workgroups;
 // every fragment then feeds one MFMA and the per-iteration overheads are paid per 32 rows: ~8 % more cycles per row).
 // SINK: learned attention sinks (fa_fwd.hpp), merged with the partner's partial in `take`
-#define NNOP_DUO_NAME fa_fwd_duo_kernel
-#define NNOP_DUO_SINK false
 #include "fa_fwd_duo_kernel.inc"
-#undef NNOP_DUO_NAME
-#undef NNOP_DUO_SINK
-#define NNOP_DUO_NAME fa_fwd_duo_sink_kernel
-#define NNOP_DUO_SINK true
-#include "fa_fwd_duo_kernel.inc"
-#undef NNOP_DUO_NAME
-#undef NNOP_DUO_SINK
-
 
 }  // namespace nnop

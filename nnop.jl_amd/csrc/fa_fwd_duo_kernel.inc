@@ -1,9 +1,8 @@
 // fa_fwd_duo_kernel.inc -- the body of fa_fwd_duo_kernel (fa_fwd_duo.hpp).
-// Included twice by fa_fwd_duo.hpp: NNOP_DUO_NAME = the kernel's name, NNOP_DUO_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false).
-template <typename T, int E, int MODE, int NZ = 2>
-__global__ __launch_bounds__(512) void NNOP_DUO_NAME(const FwdParams p) {
-    constexpr bool SINK = NNOP_DUO_SINK;
+// SINK = learned attention sinks merged in the epilogue: an instantiation of its own, so that the kernel of the calls without sinks is
+// this text with the sink code compiled away.
+template <typename T, int E, int MODE, int NZ = 2, bool SINK = false>
+__global__ __launch_bounds__(512) void fa_fwd_duo_kernel(const FwdParams p) {
     static_assert(sizeof(T) == 2 && ((E == 64 && (NZ == 1 || NZ == 2)) || (E == 128 && NZ == 1) || (E == 32 && NZ == 2)),
                   "16-bit element types; E = 64, E = 128 with 32-row waves, E = 32 with 64-row waves");
     constexpr int RW = 32 * NZ, RB = 4 * RW;                  // query rows per wave / per workgroup

@@ -1,11 +1,8 @@
 // fa_fwd_generic_kernel.inc -- the body of fa_fwd_generic_kernel (fa_generic.hpp).
-// Included four times by fa_generic.hpp: NNOP_GENERIC_NAME = the kernel's name, NNOP_GENERIC_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false), NNOP_GENERIC_CAP =
-// logit soft-capping with the runtime constants p.cap_ka / p.cap_kb (kernels of their own for the same reason).
-template <typename T>
-__global__ __launch_bounds__(256) void NNOP_GENERIC_NAME(const FwdParams p, int E, long long n_rows) {
-    constexpr bool SINK = NNOP_GENERIC_SINK;
-    constexpr bool CAP = NNOP_GENERIC_CAP;
+// SINK = learned attention sinks merged in the epilogue, CAP = logit soft-capping with the runtime constants p.cap_ka / p.cap_kb:
+// instantiations of their own, so that the kernel of the calls without them is this text with the feature compiled away.
+template <typename T, bool SINK = false, bool CAP = false>
+__global__ __launch_bounds__(256) void fa_fwd_generic_kernel(const FwdParams p, int E, long long n_rows) {
     __shared__ float qs_all[4][kGenericMaxE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + wave;

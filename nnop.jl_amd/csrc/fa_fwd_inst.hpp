@@ -49,20 +49,21 @@ static inline int fwd_params(FwdParams& p, const nnop_fa_desc& d, const FwdArgs&
     return NNOP_OK;
 }
 
-template <typename T, int E, int NW, int MODE, int QB, bool WIN = false, bool CAP = false>
+template <typename T, int E, int NW, int MODE, int QB, bool WIN = false, bool CAP = false, bool SINK = false>
 static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
+    // learned sinks: the SINK = true instantiation of the kernel (fa_fwd.hpp; the code of the calls without them stays as it is), from the
+    // SINK = true instantiation of this launcher, so that every kernel has its own LDS opt-in word below.  The other launchers likewise.
+    if constexpr (!SINK) {
+        if (a.sinks) return launch_fwd_cfg<T, E, NW, MODE, QB, WIN, CAP, true>(d, a, s);
+    }
     // 64-key tiles, except the E = 128 pair-bias body (register budget) and fp32 E = 128
     // (LDS: 2 x (K + V) x 64 keys x 512 B = 128 KiB would leave one workgroup per CU)
     constexpr int BK = (E >= 256 || (E >= 128 && (MODE == 2 || sizeof(T) == 4))) ? 32 : 64;
     constexpr int lds = fa_fwd_lds_bytes<T, E, BK>();
     static_assert(lds <= 160 * 1024, "LDS budget (160 KiB per CU on gfx950)");
-    // learned sinks: the SINK = true instantiation (the code of the calls without them stays as it is)
-    // a soft cap: the CAP = true kernels (fa_fwd.hpp), likewise
-    void (*kern)(const FwdParams);
-    if constexpr (CAP) kern = a.sinks ? fa_fwd_cap_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_cap_kernel<T, E, NW, BK, MODE, QB, WIN>;
-    else kern = a.sinks ? fa_fwd_sink_kernel<T, E, NW, BK, MODE, QB, WIN> : fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN>;
-    static unsigned long long lds_done[2] = {0, 0};
-    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
+    constexpr auto kern = fa_fwd_kernel<T, E, NW, BK, MODE, QB, WIN, SINK, CAP>;
+    static unsigned long long lds_done = 0;
+    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     if (const int st = fwd_params(p, d, a, 32 * QB * NW); st != NNOP_OK) return st;
     // Causal launches of a few rounds: pair heavy with light blocks on a CU (fa_launch.hpp causal_alt_run).  Measured (round 4,
@@ -90,13 +91,16 @@ static int launch_fwd_cfg(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
 // split-KV form (fa_fwd_split.hpp): 16 waves per workgroup, plain mode, 16-bit types, E <= 64.
 // (A v_mfma_f32_16x16x32 body of this form was built and measured 7 % slower in round 1 -- twice the MFMA issues on the port
 // that is the bottleneck; DESIGN.md section 5 -- and is no longer in the tree.)
-template <typename T, int E>
+template <typename T, int E, bool SINK = false>
 static int launch_fwd_split(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
+    if constexpr (!SINK) {
+        if (a.sinks) return launch_fwd_split<T, E, true>(d, a, s);
+    }
     constexpr int lds = fa_fwd_split_lds_bytes<T, E>();
-    void (*kern)(const FwdParams) = a.sinks ? fa_fwd_split_sink_kernel<T, E> : fa_fwd_split_kernel<T, E>;
+    constexpr auto kern = fa_fwd_split_kernel<T, E, SINK>;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static unsigned long long lds_done[2] = {0, 0};
-    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
+    static unsigned long long lds_done = 0;
+    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     if (const int st = fwd_params(p, d, a, 256); st != NNOP_OK) return st;
     hipLaunchKernelGGL(kern, dim3((unsigned)p.n_wg), dim3(1024), lds, s, p);
@@ -124,14 +128,17 @@ static inline void fwd_persist_plan(const nnop_fa_desc& d, const FwdArgs& a, Fwd
 }
 
 // 64-rows-per-wave form (fa_fwd_w64.hpp): 4 waves x 64 rows, 16-bit types, E = 64 / 128, plain and masked modes
-template <typename T, int E, int MODE, bool PRE>
+template <typename T, int E, int MODE, bool PRE, bool SINK = false>
 static int launch_fwd_w64(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
+    if constexpr (!SINK) {
+        if (a.sinks) return launch_fwd_w64<T, E, MODE, PRE, true>(d, a, s);
+    }
     constexpr int EV = E == 256 ? 128 : E;                   // E = 256: two 128-column halves of O per block (fa_fwd_w64.hpp)
     constexpr int lds = fa_fwd_w64_lds_bytes<T, E, EV>(MODE != 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = a.sinks ? fa_fwd_w64_sink_kernel<T, E, MODE, PRE, EV> : fa_fwd_w64_kernel<T, E, MODE, PRE, EV>;
-    static unsigned long long lds_done[2] = {0, 0};
-    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
+    constexpr auto kern = fa_fwd_w64_kernel<T, E, MODE, PRE, EV, SINK>;
+    static unsigned long long lds_done = 0;
+    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     if (const int st = fwd_params(p, d, a, 256); st != NNOP_OK) return st;
     long long grid = (long long)p.n_wg * (E / EV);
@@ -143,13 +150,16 @@ static int launch_fwd_w64(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s
 
 // two waves per SIMD in alternating phases (fa_fwd_duo.hpp): 8 waves, 256 query rows per workgroup, 16-bit types, E = 64
 // (NZ = 1: 32 rows per wave, 128 per workgroup -- fwd_duo_nz below)
-template <typename T, int E, int MODE, int NZ>
+template <typename T, int E, int MODE, int NZ, bool SINK = false>
 static int launch_fwd_duo(const nnop_fa_desc& d, const FwdArgs& a, hipStream_t s) {
+    if constexpr (!SINK) {
+        if (a.sinks) return launch_fwd_duo<T, E, MODE, NZ, true>(d, a, s);
+    }
     constexpr int lds = fa_fwd_duo_lds_bytes<T, E>(MODE != 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = a.sinks ? fa_fwd_duo_sink_kernel<T, E, MODE, NZ> : fa_fwd_duo_kernel<T, E, MODE, NZ>;
-    static unsigned long long lds_done[2] = {0, 0};
-    if (ensure_dynamic_lds(kern, lds, &lds_done[a.sinks ? 1 : 0]) != NNOP_OK) return NNOP_ERR_HIP;
+    constexpr auto kern = fa_fwd_duo_kernel<T, E, MODE, NZ, SINK>;
+    static unsigned long long lds_done = 0;
+    if (ensure_dynamic_lds(kern, lds, &lds_done) != NNOP_OK) return NNOP_ERR_HIP;
     FwdParams p;
     if (const int st = fwd_params(p, d, a, 128 * NZ); st != NNOP_OK) return st;
     long long grid = p.n_wg;
@@ -336,12 +346,10 @@ template <typename T> static int launch_fwd_generic(const nnop_fa_desc& d, const
     const long long n_rows = (long long)d.batch * d.qh * d.ql;
     const long long grid = (n_rows + 3) / 4;
     if (grid > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    if (a.softcap != 0.f) {
-        if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_cap_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
-        else hipLaunchKernelGGL((fa_fwd_generic_cap_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
-    } else
-    if (a.sinks) hipLaunchKernelGGL((fa_fwd_generic_sink_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
-    else hipLaunchKernelGGL((fa_fwd_generic_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
+    const bool sink = a.sinks != nullptr, cap = a.softcap != 0.f;
+    const auto kern = cap ? (sink ? fa_fwd_generic_kernel<T, true, true> : fa_fwd_generic_kernel<T, false, true>)
+                          : (sink ? fa_fwd_generic_kernel<T, true, false> : fa_fwd_generic_kernel<T, false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, s, p, d.emb, n_rows);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 

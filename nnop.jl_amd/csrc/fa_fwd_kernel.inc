@@ -1,11 +1,8 @@
 // fa_fwd_kernel.inc -- the body of fa_fwd_kernel (fa_fwd.hpp).
-// Included four times by fa_fwd.hpp: NNOP_FWD_NAME = the kernel's name, NNOP_FWD_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false), NNOP_FWD_CAP =
-// logit soft-capping in finish_x (kernels of their own for the same reason).
-template <typename T, int E, int NW, int BK, int MODE, int QB, bool WIN = false>
-__global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) ? 1 : 2) void NNOP_FWD_NAME(const FwdParams p) {
-    constexpr bool SINK = NNOP_FWD_SINK;
-    constexpr bool CAP = NNOP_FWD_CAP;
+// SINK = learned attention sinks merged in the epilogue, CAP = logit soft-capping in finish_x: instantiations of their own, so that the
+// kernel of the calls without them is this text with the feature compiled away.
+template <typename T, int E, int NW, int BK, int MODE, int QB, bool WIN = false, bool SINK = false, bool CAP = false>
+__global__ __launch_bounds__(NW * 64, (QB == 2 || (sizeof(T) == 4 && E >= 256)) ? 1 : 2) void fa_fwd_kernel(const FwdParams p) {
     using frag_t = typename Elem<T>::frag;
     using KImg   = RowImg<T, E>;
     using VImg   = ColImg<T, E>;

@@ -261,9 +261,7 @@ __device__ __forceinline__ void fa_fwd_split_body(const FwdParams p) {
     }
 }
 
-template <typename T, int E>
-__global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) { fa_fwd_split_body<T, E, false>(p); }
-template <typename T, int E>
-__global__ __launch_bounds__(1024) void fa_fwd_split_sink_kernel(const FwdParams p) { fa_fwd_split_body<T, E, true>(p); }
+template <typename T, int E, bool SINK = false>
+__global__ __launch_bounds__(1024) void fa_fwd_split_kernel(const FwdParams p) { fa_fwd_split_body<T, E, SINK>(p); }
 
 }  // namespace nnop

@@ -289,16 +289,6 @@ template <typename T, int E, int EV = E> constexpr int fa_fwd_w64_lds_bytes(bool
 // be the whole accumulator file: the grid then holds every block twice, each copy contracting Q K^T over all of E (Q fragments: 128
 // registers) but accumulating one 128-column half of O (+33 % MFMA work for a spill-free kernel; the 32-row form spills 62-152).
 // SINK: learned attention sinks (fa_fwd.hpp), merged in the epilogue
-#define NNOP_W64_NAME fa_fwd_w64_kernel
-#define NNOP_W64_SINK false
 #include "fa_fwd_w64_kernel.inc"
-#undef NNOP_W64_NAME
-#undef NNOP_W64_SINK
-#define NNOP_W64_NAME fa_fwd_w64_sink_kernel
-#define NNOP_W64_SINK true
-#include "fa_fwd_w64_kernel.inc"
-#undef NNOP_W64_NAME
-#undef NNOP_W64_SINK
-
 
 }  // namespace nnop

@@ -1,9 +1,8 @@
 // fa_fwd_w64_kernel.inc -- the body of fa_fwd_w64_kernel (fa_fwd_w64.hpp).
-// Included twice by fa_fwd_w64.hpp: NNOP_W64_NAME = the kernel's name, NNOP_W64_SINK = learned attention sinks merged in the epilogue (a
-// kernel of its own, so that the kernel of the calls without sinks is compiled from exactly this text with SINK = false).
-template <typename T, int E, int MODE, bool PRE, int EV = E>
-__global__ __launch_bounds__(256, 1) void NNOP_W64_NAME(const FwdParams p_arg) {
-    constexpr bool SINK = NNOP_W64_SINK;
+// SINK = learned attention sinks merged in the epilogue: an instantiation of its own, so that the kernel of the calls without sinks is
+// this text with the sink code compiled away.
+template <typename T, int E, int MODE, bool PRE, int EV = E, bool SINK = false>
+__global__ __launch_bounds__(256, 1) void fa_fwd_w64_kernel(const FwdParams p_arg) {
     static_assert(sizeof(T) == 2 && ((EV == E && (E == 64 || E == 128)) || (E == 256 && EV == 128)), "16-bit element types, E = 64, 128 or 256 (two 128-column halves)");
     using frag_t = typename Elem<T>::frag;
     using KImg   = RowImg<T, E>;

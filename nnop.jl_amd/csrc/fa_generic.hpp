@@ -46,31 +46,7 @@ NNOP_DEV void generic_key_range(int causal, int wl, int wr, int qi, int KL, int&
     kbeg = (wl >= 0 && qi - wl > 0) ? qi - wl : 0;
 }
 
-#define NNOP_GENERIC_NAME fa_fwd_generic_kernel
-#define NNOP_GENERIC_SINK false
-#define NNOP_GENERIC_CAP false
 #include "fa_fwd_generic_kernel.inc"
-#undef NNOP_GENERIC_NAME
-#undef NNOP_GENERIC_SINK
-#define NNOP_GENERIC_NAME fa_fwd_generic_sink_kernel
-#define NNOP_GENERIC_SINK true
-#include "fa_fwd_generic_kernel.inc"
-#undef NNOP_GENERIC_NAME
-#undef NNOP_GENERIC_SINK
-#undef NNOP_GENERIC_CAP
-#define NNOP_GENERIC_CAP true
-#define NNOP_GENERIC_NAME fa_fwd_generic_cap_kernel
-#define NNOP_GENERIC_SINK false
-#include "fa_fwd_generic_kernel.inc"
-#undef NNOP_GENERIC_NAME
-#undef NNOP_GENERIC_SINK
-#define NNOP_GENERIC_NAME fa_fwd_generic_cap_sink_kernel
-#define NNOP_GENERIC_SINK true
-#include "fa_fwd_generic_kernel.inc"
-#undef NNOP_GENERIC_NAME
-#undef NNOP_GENERIC_SINK
-#undef NNOP_GENERIC_CAP
-
 
 // lse = ms + log(ls) (natural units; -inf for a row without a visible key) and delta = sum_e dO * o, per query row
 template <typename T>
@@ -91,7 +67,7 @@ __global__ __launch_bounds__(256) void fa_bwd_generic_pre_kernel(const BwdParams
     }
 }
 
-// (body shared by fa_bwd_generic_dq_kernel and its soft-capped twin fa_bwd_generic_dq_cap_kernel; CAP = false compiles the cap away)
+// (body of fa_bwd_generic_dq_kernel; CAP = logit soft-capping, CAP = false compiles the cap away)
 template <typename T, bool CAP>
 NNOP_DEV void fa_bwd_generic_dq_body(const BwdParams& p, int E, long long n_rows) {
     __shared__ float qs_all[4][kGenericMaxE], dos_all[4][kGenericMaxE];
@@ -151,13 +127,9 @@ NNOP_DEV void fa_bwd_generic_dq_body(const BwdParams& p, int E, long long n_rows
     }
 }
 
-template <typename T>
+template <typename T, bool CAP = false>
 __global__ __launch_bounds__(256) void fa_bwd_generic_dq_kernel(const BwdParams p, int E, long long n_rows) {
-    fa_bwd_generic_dq_body<T, false>(p, E, n_rows);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void fa_bwd_generic_dq_cap_kernel(const BwdParams p, int E, long long n_rows) {
-    fa_bwd_generic_dq_body<T, true>(p, E, n_rows);
+    fa_bwd_generic_dq_body<T, CAP>(p, E, n_rows);
 }
 
 template <typename T, bool CAP>
@@ -228,13 +200,9 @@ NNOP_DEV void fa_bwd_generic_dkdv_body(const BwdParams& p, int E, long long n_kr
         }
     }
 }
-template <typename T>
+template <typename T, bool CAP = false>
 __global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_kernel(const BwdParams p, int E, long long n_krows) {
-    fa_bwd_generic_dkdv_body<T, false>(p, E, n_krows);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void fa_bwd_generic_dkdv_cap_kernel(const BwdParams p, int E, long long n_krows) {
-    fa_bwd_generic_dkdv_body<T, true>(p, E, n_krows);
+    fa_bwd_generic_dkdv_body<T, CAP>(p, E, n_krows);
 }
 
 }  // namespace nnop

@@ -61,15 +61,18 @@ def test_phase_structure_of_the_loop():
 def test_compiled_kernels_allocate_within_the_loops_register_map():
     from audit_w64 import compile_asm                        # (the library's flags; shares its cache with tests/test_w64_codegen.py)
     text = compile_asm("fa_fwd_bf16.hip", [])
-    got = {}
-    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi64ELi(\d)ELi(\d)EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
-        got[(int(m.group(1)), int(m.group(2)), m.group(3))] = int(m.group(4))
-    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi128ELi(\d)ELi1EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
-        got[(int(m.group(1)), 128, m.group(2))] = int(m.group(3))
-    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi32ELi(\d)ELi2EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
-        got[(int(m.group(1)), 32, m.group(2))] = int(m.group(3))
+    got = {}                                                  # (MODE, rows per wave / 32 at E = 64 or the E of the other loops, SINK, figure)
+    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi64ELi(\d)ELi(\d)ELb([01])EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
+        got[(int(m.group(1)), int(m.group(2)), int(m.group(3)), m.group(4))] = int(m.group(5))
+    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi128ELi(\d)ELi1ELb([01])EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
+        got[(int(m.group(1)), 128, int(m.group(2)), m.group(3))] = int(m.group(4))
+    for m in re.finditer(r"\.set _ZN4nnop17fa_fwd_duo_kernelIDF16bLi32ELi(\d)ELi2ELb([01])EEEvNS_9FwdParamsE\.(num_vgpr|num_agpr|private_seg_size), (\d+)", text):
+        got[(int(m.group(1)), 32, int(m.group(2)), m.group(3))] = int(m.group(4))
+    assert len(got) == 2 * 4 * 2 * 3, got                     # {plain, masked} x the four loops x {SINK = false, true} x three figures
     for nz in (1, 2, 128, 32):                                # rows per wave / 32 at E = 64; the E = 128 loop; the E = 32 loop
-        assert got[(0, nz, "num_vgpr")] <= 256 and got[(1, nz, "num_vgpr")] <= 256 and got[(0, nz, "num_agpr")] == 0 and got[(1, nz, "num_agpr")] == 0, got
-        # plain mode: nothing spilled; masked mode (persistent block loop around the statement): a few prologue / epilogue values park in
-        # scratch around -- never inside -- the loop, once per block
-        assert got[(0, nz, "private_seg_size")] == 0 and got[(1, nz, "private_seg_size")] <= 64, got
+        for sink in (0, 1):                                   # the sink merge sits in the epilogue: the same bounds hold with and without it
+            assert got[(0, nz, sink, "num_vgpr")] <= 256 and got[(1, nz, sink, "num_vgpr")] <= 256, got
+            assert got[(0, nz, sink, "num_agpr")] == 0 and got[(1, nz, sink, "num_agpr")] == 0, got
+            # plain mode: nothing spilled; masked mode (persistent block loop around the statement): a few prologue / epilogue values park in
+            # scratch around -- never inside -- the loop, once per block
+            assert got[(0, nz, sink, "private_seg_size")] == 0 and got[(1, nz, sink, "private_seg_size")] <= 64, got
