@@ -3,7 +3,6 @@ four entry points are declared, bound and exported; they validate as the plain n
 Python wrappers refuse CPU tensors and a mismatched residual; and the reference the GPU tests are judged against (tests/addnorm_ref.py)
 has the right gradient -- one array, for x and for residual alike."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -11,14 +10,14 @@ import pytest
 import torch
 
 import addnorm_ref as ref
+from abi_util import HEADER, SHIM, strip_c_comments
 from oracle.naive_norms import naive_layer_norm, naive_rms_norm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("nnop_add_rms_norm", "nnop_add_rms_norm_bwd", "nnop_add_layer_norm", "nnop_add_layer_norm_bwd")
 
 
 def test_exports(pkg):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nnop_hip.h")).read(), flags=re.S)
+    header = strip_c_comments(open(HEADER).read())
     declared = set(re.findall(r"\b(nnop_[a-z_]+)\s*\(", header))
     lib = pkg._lib.load()
     for name in NEW:
@@ -201,7 +200,7 @@ def test_reference_rounds_h_once():
 
 
 def test_shim_source_names_the_symbols():
-    src = open(os.path.join(ROOT, "nnop.jl_amd", "julia", "NNopHIPExt.jl")).read()
+    src = open(SHIM).read()
     for name in NEW:
         assert re.search(r":%s\b" % name, src), f"the Julia shim does not ccall {name}"
     for fn in ("add_rms_norm", "add_layer_norm"):

@@ -1,89 +1,14 @@
-"""Learned attention sinks on the GPU: parity with the fp64 oracle through tests/sink_ref.py on every forward form and backward
+"""Learned attention sinks on the GPU: parity with the fp64 oracle through tests/attn_ref.py on every forward form and backward
 path, the properties of include/nnop_hip.h (rows without keys, large sigma, sigma = -inf), a dsinks that is bitwise the same
 whichever backward kernels ran, autograd, and a gpt-oss-like layer at full size."""
-import zlib
-
 import numpy as np
 import pytest
 import torch
 
-from sink_ref import sink_fwd, sink_grads
-from util import TORCH_DT, assert_close
-from window_ref import dead_rows
+from attn_ref import INF, attention_fwd, check_parity, inputs, run
+from util import TORCH_DT, assert_close, to64
 
 pytestmark = pytest.mark.gpu
-
-INF = float("inf")
-MIX = [-INF, -30.0, 0.0, 3.0, 30.0]
-
-
-def _inputs(key, B, QH, KH, QL, KL, E, dt, dev, pair=False, pad=False, sinks=None):
-    rng = np.random.default_rng(zlib.crc32(repr(key).encode()))
-    mk = lambda *s: torch.tensor(rng.standard_normal(s).astype(np.float32)).to(torch.bfloat16).to(TORCH_DT[dt]).to(dev)
-    d = dict(q=mk(B, QH, QL, E), k=mk(B, KH, KL, E), v=mk(B, KH, KL, E), do=mk(B, QH, QL, E))
-    d["pair"] = mk(B, KL, QL, QH) if pair else None
-    d["mask"] = None
-    if pad:
-        lens = rng.integers(max(1, KL // 3), KL + 1, size=B)
-        d["mask"] = torch.tensor(np.arange(KL)[None, :] < lens[:, None]).to(dev)
-    s = [MIX[(i + len(repr(key))) % len(MIX)] for i in range(QH)] if sinks is None else sinks
-    d["sinks"] = torch.tensor(s, dtype=torch.float32, device=dev)
-    return d
-
-
-def _np(t):
-    return None if t is None else t.detach().double().cpu().numpy()
-
-
-def _run(pkg, d, causal, window=None):
-    q, k, v, do, pair, mask, s = d["q"], d["k"], d["v"], d["do"], d["pair"], d["mask"], d["sinks"]
-    o, ms, ls = pkg._flash_attention(q, k, v, pair, causal=causal, kpad_mask=mask, window=window, sinks=s)
-    g = pkg.grad_flash_attention(do, o, ms, ls, q, k, v, pair, causal=causal, kpad_mask=mask, window=window, sinks=s)
-    torch.cuda.synchronize()
-    return (o, ms, ls), g
-
-
-def _check(pkg, d, dt, causal, window=None):
-    """the library against sink_ref; rows of sigma = -inf heads that see no key follow window_ref's dead-row convention"""
-    (o, ms, ls), (dq, dk, dv, dp, ds) = _run(pkg, d, causal, window)
-    q, k, v, do = (_np(d[n]) for n in ("q", "k", "v", "do"))
-    sinks, m = _np(d["sinks"]), (None if d["mask"] is None else d["mask"].cpu().numpy())
-    dead = dead_rows(q, k, causal=causal, kpad_mask=m, window=window) & np.isneginf(sinks)[None, :, None]
-    # a dead row of a head without a sink: NaN o, ms = -inf, dq = 0, no contribution (_grads_dead_safe)
-    o_ref, ms_ref, ls_ref = sink_fwd(q, k, v, sinks, _np(d["pair"]), causal=causal, kpad_mask=m, window=window)
-    live = ~dead
-    assert np.isnan(_np(o)[dead]).all() and np.isneginf(_np(ms)[dead]).all()
-    assert_close("o", _np(o)[live], o_ref[live], dt, floor=True)
-    assert_close("ms", _np(ms)[live], ms_ref[live], dt, floor=True)
-    assert_close("ls", _np(ls)[live], ls_ref[live], dt, 2.0, floor=True)
-    if dead.any():
-        do = np.where(dead[..., None], 0.0, do)
-        rq, rk, rv, rp, rs = _grads_dead_safe(q, k, v, do, sinks, _np(d["pair"]), causal, m, window, dead)
-    else:
-        rq, rk, rv, rp, rs = sink_grads(q, k, v, do, sinks, _np(d["pair"]), causal=causal, kpad_mask=m, window=window)
-    sc = 1.0 if dt == "f32" else 2.0
-    assert (_np(dq)[dead] == 0).all()
-    assert_close("dq", dq, rq, dt, sc, floor=True, kind="grad")
-    assert_close("dk", dk, rk, dt, sc, floor=True, kind="grad")
-    assert_close("dv", dv, rv, dt, sc, floor=True, kind="grad")
-    if d["pair"] is not None:
-        assert_close("dpair", dp, rp, dt, sc, floor=True, kind="grad")
-    assert_close("dsinks", ds, rs, dt, sc, floor=True, kind="grad")
-    assert (_np(ds)[np.isneginf(sinks)] == 0).all()
-
-
-def _grads_dead_safe(q, k, v, do, sinks, pair, causal, m, window, dead):
-    """sink_grads where rows of sigma = -inf heads see no key: those rows see every key with a zero cotangent (window_grads'
-    convention), through an explicit visibility bias"""
-    from window_ref import window_keep
-    B, QH, QL, _ = q.shape
-    KL = k.shape[2]
-    vis = window_keep(QL, KL, window, causal)[None, None] & (np.ones((B, KL), bool) if m is None else m)[:, None, None, :]
-    vis = vis | dead[..., None]
-    bias = np.transpose(np.where(vis, 0.0, -INF), (0, 3, 2, 1))
-    tot = bias if pair is None else pair + bias
-    rq, rk, rv, rp, rs = sink_grads(q, k, v, do, sinks, tot, causal=False)
-    return rq, rk, rv, (rp if pair is not None else None), rs
 
 
 # ---- parity grid: dtype x E x causal x ragged lengths x kpad x window x pair x GQA, pruned ------------------------------------
@@ -110,8 +35,8 @@ def test_sinks_parity(pkg, dev, case):
     QH, KH = (5, 5) if not gqa else (6, 2)
     if pair:
         QH, KH = 5, 5
-    d = _inputs(case, 2, QH, KH, QL, KL, E, dt, dev, pair=pair, pad=pad)
-    _check(pkg, d, dt, causal, window)
+    d = inputs(case, 2, QH, KH, QL, KL, E, dt, dev, pair=pair, pad=pad, sinks="mix")
+    check_parity(pkg, d, dt, causal, window=window, sinks=d["sinks"])
 
 
 # ---- every forward form on purpose, pinned -----------------------------------------------------------------------------------
@@ -143,14 +68,14 @@ FORMS = [
 def test_every_forward_form(pkg, dev, tune, form):
     name, knobs, dt, E, QL, KL, QH, KH, B, causal, window, pad, want = form
     tune(**knobs)
-    d = _inputs(form[0], B, QH, KH, QL, KL, E, dt, dev, pad=pad)
+    d = inputs(form[0], B, QH, KH, QL, KL, E, dt, dev, pad=pad, sinks="mix")
     assert pkg._lib.fwd_form(_desc(pkg, d, causal), has_mask=pad, window=window) == want
-    _check(pkg, d, dt, causal, window)
+    check_parity(pkg, d, dt, causal, window=window, sinks=d["sinks"])
 
 
 def test_persistent_forward_is_the_one_block_result(pkg, dev, tune):
     """the persistent block-list form (w64 and duo, causal) against the one-block-per-workgroup form: the same rows, bitwise"""
-    d = _inputs("persist", 2, 8, 2, 8192, 8192, 64, "bf16", dev)
+    d = inputs("persist", 2, 8, 2, 8192, 8192, 64, "bf16", dev, sinks="mix")
     for knobs in (dict(fwd_duo=0, fwd_w64=1), dict(fwd_duo=1)):
         outs = []
         for persist in (0, 1):
@@ -177,29 +102,27 @@ BWD = [
 def test_every_backward_path(pkg, dev, tune, form):
     """each backward path, pinned, against the reference; dsinks is the same bits whichever path ran (it reads dO, o, ms, ls only)"""
     name, knobs, want = form
-    d = _inputs("bwd", 2, 8, 2, 700, 700, 64, "bf16", dev)
-    ref = _run(pkg, d, True)[1]                                    # the default path
+    d = inputs("bwd", 2, 8, 2, 700, 700, 64, "bf16", dev, sinks="mix")
+    ref = run(pkg, d, True, sinks=d["sinks"])                      # the default path
     tune(**knobs)
     assert pkg._lib.bwd_kernels(_desc(pkg, d, True)) == want
-    _check(pkg, d, "bf16", True)
-    got = _run(pkg, d, True)[1]
-    assert torch.equal(got[4], ref[4])
+    got = check_parity(pkg, d, "bf16", True, sinks=d["sinks"])
+    assert torch.equal(got[7], ref[7])
 
 
 def test_generic_backward(pkg, dev):
     """E = 8: the plain-HIP backward kernels (fa_generic.hpp; every embedding dim outside the tiled set)"""
-    d = _inputs("bwd-generic", 2, 4, 2, 300, 280, 8, "f16", dev, pad=True)
+    d = inputs("bwd-generic", 2, 4, 2, 300, 280, 8, "f16", dev, pad=True, sinks="mix")
     assert pkg._lib.fwd_form(_desc(pkg, d, True), has_mask=True) == "fa_fwd_generic_kernel"
-    _check(pkg, d, "f16", True, (50, 0))
+    check_parity(pkg, d, "f16", True, window=(50, 0), sinks=d["sinks"])
 
 
 @pytest.mark.parametrize("dt,E", [("bf16", 64), ("f32", 32), ("f16", 128)])
 def test_pair_bias_staged_and_direct(pkg, dev, dt, E):
     from importlib import import_module
     att = import_module(pkg.__name__ + ".attention")
-    d = _inputs(("pair", dt, E), 1, 4, 4, 200, 150, E, dt, dev, pair=True)
-    _check(pkg, d, dt, False)                         # grad_flash_attention: the staged path
-    (o, ms, ls), ref = _run(pkg, d, False)
+    d = inputs(("pair", dt, E), 1, 4, 4, 200, 150, E, dt, dev, pair=True, sinks="mix")
+    o, ms, ls, *ref = check_parity(pkg, d, dt, False, sinks=d["sinks"])       # grad_flash_attention: the staged path
     q, k, v = d["q"], d["k"], d["v"]
     small = att.bwd_workspace_bytes(q, k, v, causal=False)
     ws = torch.empty(small, dtype=torch.uint8, device=dev)
@@ -209,27 +132,26 @@ def test_pair_bias_staged_and_direct(pkg, dev, dt, E):
     torch.cuda.synchronize()
     assert torch.equal(ds, ref[4])
     for a, b in zip((dq, dk, dv, dp), ref[:4]):
-        assert_close("direct pair", a, _np(b), dt, 2.0, floor=True, kind="grad")
+        assert_close("direct pair", a, to64(b), dt, 2.0, floor=True, kind="grad")
 
 
 # ---- properties -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt,E", [("bf16", 64), ("f32", 16), ("f16", 8)])
 def test_rows_without_keys_see_only_the_sink(pkg, dev, dt, E):
-    d = _inputs(("dead", dt), 1, 2, 2, 256, 256, E, dt, dev, sinks=[0.5, -2.0])
+    d = inputs(("dead", dt), 1, 2, 2, 256, 256, E, dt, dev, sinks=[0.5, -2.0])
     mask = torch.zeros(1, 256, dtype=torch.bool, device=dev)
     mask[0, 200:] = True                               # causal + window (10, 0): rows < 200 see nothing
     d["mask"] = mask
-    (o, ms, ls), (dq, *_rest) = _run(pkg, d, True, (10, 0))
+    o, ms, ls, dq, *_rest = check_parity(pkg, d, dt, True, window=(10, 0), sinks=d["sinks"])
     assert (o[:, :, :200] == 0).all() and (dq[:, :, :200] == 0).all()
     assert torch.isfinite(ms).all() and torch.isfinite(ls).all()
-    _check(pkg, d, dt, True, (10, 0))
 
 
 @pytest.mark.parametrize("dt,E", [("bf16", 64), ("f16", 128), ("f32", 32), ("bf16", 8)])
 def test_large_sink_does_not_overflow(pkg, dev, dt, E):
-    d = _inputs(("big", dt, E), 1, 2, 1, 300, 300, E, dt, dev, sinks=[200.0, 200.0])
+    d = inputs(("big", dt, E), 1, 2, 1, 300, 300, E, dt, dev, sinks=[200.0, 200.0])
     d["q"] = d["q"] * 0.01
-    (o, ms, ls), g = _run(pkg, d, False)
+    o, ms, ls, *g = run(pkg, d, False, sinks=d["sinks"])
     for t in (o, ms, ls) + tuple(g[:3]) + (g[4],):
         assert torch.isfinite(t).all()
     assert o.float().abs().max() < 1e-30 and ((ms.float() - 200).abs() < 1e-3).all() and ((ls.float() - 1).abs() < 1e-2).all()
@@ -238,23 +160,23 @@ def test_large_sink_does_not_overflow(pkg, dev, dt, E):
 @pytest.mark.parametrize("dt,E,causal,pad", [("bf16", 64, False, False), ("f16", 128, True, True), ("f32", 32, True, False),
                                              ("bf16", 8, False, True)])
 def test_minus_inf_sinks_are_the_call_without_sinks(pkg, dev, dt, E, causal, pad):
-    d = _inputs(("noinf", dt, E), 2, 4, 2, 1100, 1100, E, dt, dev, pad=pad, sinks=[-INF] * 4)
-    (o, ms, ls), (dq, dk, dv, _, ds) = _run(pkg, d, causal)
+    d = inputs(("noinf", dt, E), 2, 4, 2, 1100, 1100, E, dt, dev, pad=pad, sinks=[-INF] * 4)
+    o, ms, ls, dq, dk, dv, _, ds = run(pkg, d, causal, sinks=d["sinks"])
     o2, ms2, ls2 = pkg._flash_attention(d["q"], d["k"], d["v"], causal=causal, kpad_mask=d["mask"])
     dq2, dk2, dv2, _ = pkg.grad_flash_attention(d["do"], o2, ms2, ls2, d["q"], d["k"], d["v"], causal=causal, kpad_mask=d["mask"])
     # the sink kernels are compiled apart from the kernels without sinks (whose code stays exactly as it was), so the two may round
     # differently in the last place (e.g. where the compiler contracts a multiply-add); the NaN pattern and dsinks = 0 are exact
     for name, a, b in (("o", o, o2), ("ms", ms, ms2), ("ls", ls, ls2)):
         assert (torch.isnan(a) == torch.isnan(b)).all()
-        assert_close(name, a, _np(b), dt, floor=True)
+        assert_close(name, a, to64(b), dt, floor=True)
     for name, a, b in (("dq", dq, dq2), ("dk", dk, dk2), ("dv", dv, dv2)):
-        assert_close(name, a, _np(b), dt, floor=True, kind="grad")
+        assert_close(name, a, to64(b), dt, floor=True, kind="grad")
     assert (ds == 0).all()
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_autograd_through_flash_attention(pkg, dev, dt):
-    d = _inputs(("ag", dt), 2, 4, 2, 257, 257, 64, dt, dev, sinks=[0.5, -1.0, 2.0, -INF])
+    d = inputs(("ag", dt), 2, 4, 2, 257, 257, 64, dt, dev, sinks=[0.5, -1.0, 2.0, -INF])
     leaves = [d[n].clone().requires_grad_(True) for n in ("q", "k", "v")]
     s = d["sinks"].to(TORCH_DT[dt]).clone().requires_grad_(True)
     o = pkg.flash_attention(*leaves, causal=True, window=(60, 0), sinks=s)
@@ -275,16 +197,16 @@ def test_gptoss_layer(pkg, dev, window):
     L, QH, KH = 4096, 64, 8
     rng = np.random.default_rng(7)
     sk = rng.standard_normal(QH).astype(np.float32)
-    d = _inputs(("gptoss", window), 1, QH, KH, L, L, 64, "bf16", dev, sinks=list(sk))
-    (o, ms, ls), (dq, dk, dv, _, ds) = _run(pkg, d, True, window)
+    d = inputs(("gptoss", window), 1, QH, KH, L, L, 64, "bf16", dev, sinks=list(sk))
+    o, ms, ls, dq, dk, dv, _, ds = run(pkg, d, True, window=window, sinks=d["sinks"])
     R = 512
     for kh in (0, 5):
         hs = slice(kh * 8, kh * 8 + 8)
-        sub = lambda t: _np(t[:, hs, :R]) if t.shape[1] == QH else _np(t[:, kh:kh + 1, :R])
-        o_ref, ms_ref, ls_ref = sink_fwd(sub(d["q"]), sub(d["k"]), sub(d["v"]), sk[hs].astype(np.float64), causal=True,
-                                         window=window)
+        sub = lambda t: to64(t[:, hs, :R]) if t.shape[1] == QH else to64(t[:, kh:kh + 1, :R])
+        o_ref, ms_ref, ls_ref = attention_fwd(sub(d["q"]), sub(d["k"]), sub(d["v"]), causal=True, window=window,
+                                              sinks=sk[hs].astype(np.float64))
         assert_close("o", o[:, hs, :R], o_ref, "bf16", floor=True)
-        assert_close("ms", _np(ms[:, hs, :R]), ms_ref, "bf16", floor=True)
-        assert_close("ls", _np(ls[:, hs, :R]), ls_ref, "bf16", 2.0, floor=True)
-    want = -(np.exp(sk.astype(np.float64)[None, :, None] - _np(ms)) / _np(ls) * (_np(d["do"]) * _np(o)).sum(-1)).sum(axis=(0, 2))
-    np.testing.assert_allclose(_np(ds), want, rtol=2e-5, atol=1e-3)
+        assert_close("ms", to64(ms[:, hs, :R]), ms_ref, "bf16", floor=True)
+        assert_close("ls", to64(ls[:, hs, :R]), ls_ref, "bf16", 2.0, floor=True)
+    want = -(np.exp(sk.astype(np.float64)[None, :, None] - to64(ms)) / to64(ls) * (to64(d["do"]) * to64(o)).sum(-1)).sum(axis=(0, 2))
+    np.testing.assert_allclose(to64(ds), want, rtol=2e-5, atol=1e-3)

@@ -1,19 +1,14 @@
 """CPU tests of learned attention sinks: the sink reference against a literal torch implementation of gpt-oss's formula (cat,
 softmax, drop), the validation codes of nnop_fa_fwd_sinks / nnop_fa_bwd_sinks, and the Julia shim's declarations."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-from sink_ref import sink_fwd, sink_grads
-from window_ref import window_keep
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "nnop_hip.h")
-SHIM = os.path.join(ROOT, "nnop.jl_amd", "julia", "NNopHIPExt.jl")
+from abi_util import HEADER, SHIM, c_param_count, fa_desc, fa_opts, jl_ccall_types, strip_c_comments
+from attn_ref import attention_fwd, attention_grads, window_keep
 
 
 # ---- the reference against the literal formula --------------------------------------------------------------------------------
@@ -54,8 +49,8 @@ def test_reference_matches_the_gptoss_formula(case):
         mask = np.ones((B, KL), bool)
         mask[:, -3:] = False
     sinks = np.array(sk)
-    o, ms, ls = sink_fwd(q, k, v, sinks, pair, causal=causal, kpad_mask=mask, window=window)
-    dq, dk, dv, dp, ds = sink_grads(q, k, v, do, sinks, pair, causal=causal, kpad_mask=mask, window=window)
+    o, ms, ls = attention_fwd(q, k, v, pair, causal=causal, kpad_mask=mask, window=window, sinks=sinks)
+    dq, dk, dv, dp, ds = attention_grads(q, k, v, do, pair, causal=causal, kpad_mask=mask, window=window, sinks=sinks)
 
     t = lambda x: torch.tensor(x, dtype=torch.float64, requires_grad=True)
     tq, tk, tv, ts = t(q), t(k), t(v), t(sinks)
@@ -89,8 +84,8 @@ def test_dsinks_is_minus_p_sink_times_delta():
     B, QH, KH, QL, KL, E = 2, 4, 2, 10, 13, 8
     q, k, v, do = (rng.standard_normal(s) for s in ((B, QH, QL, E), (B, KH, KL, E), (B, KH, KL, E), (B, QH, QL, E)))
     sinks = np.array([0.3, -1.0, 2.5, 30.0])
-    o, ms, ls = sink_fwd(q, k, v, sinks, causal=True)
-    ds = sink_grads(q, k, v, do, sinks, causal=True)[4]
+    o, ms, ls = attention_fwd(q, k, v, causal=True, sinks=sinks)
+    ds = attention_grads(q, k, v, do, causal=True, sinks=sinks)[4]
     want = -(np.exp(sinks[None, :, None] - ms) / ls * (do * o).sum(-1)).sum(axis=(0, 2))
     np.testing.assert_allclose(ds, want, rtol=1e-10)
 
@@ -102,27 +97,14 @@ def test_row_without_keys_sees_only_the_sink():
     mask = np.zeros((1, 6), bool)
     mask[0, 4:] = True                                   # with window (1, 0) rows 0..2 see nothing
     sinks = np.array([0.7, -3.0])
-    o, ms, ls = sink_fwd(q, k, v, sinks, causal=True, kpad_mask=mask, window=(1, 0))
-    dq, _, _, _, _ = sink_grads(q, k, v, do, sinks, causal=True, kpad_mask=mask, window=(1, 0))
+    o, ms, ls = attention_fwd(q, k, v, causal=True, kpad_mask=mask, window=(1, 0), sinks=sinks)
+    dq, _, _, _, _ = attention_grads(q, k, v, do, causal=True, kpad_mask=mask, window=(1, 0), sinks=sinks)
     assert (o[:, :, :3] == 0).all() and (dq[:, :, :3] == 0).all()
     np.testing.assert_array_equal(ms[:, :, :3], np.broadcast_to(sinks[None, :, None], (1, 2, 3)))
     np.testing.assert_array_equal(ls[:, :, :3], 1.0)
 
 
 # ---- C ABI validation (NULL tensors: the checks run before any pointer is used) ------------------------------------------------
-def _desc(pkg, **kw):
-    base = dict(dtype=pkg._lib.NNOP_BF16, emb=64, ql=128, kl=128, qh=4, kh=4, batch=2, causal=0)
-    base.update(kw)
-    return pkg._lib.FaDesc(**base)
-
-
-def _opts(pkg, left=-1, right=-1, reserved=None):
-    o = pkg._lib.FaOpts(window_left=left, window_right=right)
-    for i, r in enumerate(reserved or []):
-        o.reserved[i] = r
-    return o
-
-
 def _fwd(lib, d, opts, sinks, tensors=None):
     t = C.c_void_p(tensors) if tensors else C.c_void_p(0)
     op = C.byref(opts) if opts is not None else None
@@ -145,8 +127,8 @@ def _sinks_calls(lib, d, opts, sinks, dsinks):
 def test_sinks_null_is_the_ex_call(pkg):
     lib = pkg._lib.load()
     null = C.c_void_p(0)
-    for d, opts in ((_desc(pkg), None), (_desc(pkg), _opts(pkg, 3, 0)), (_desc(pkg, emb_k=32), None),
-                    (_desc(pkg), _opts(pkg, reserved=[1]))):
+    for d, opts in ((fa_desc(pkg), None), (fa_desc(pkg), fa_opts(pkg, 3, 0)), (fa_desc(pkg, emb_k=32), None),
+                    (fa_desc(pkg), fa_opts(pkg, reserved=[1]))):
         op = C.byref(opts) if opts is not None else None
         ex_f = lib.nnop_fa_fwd_ex(C.byref(d), op, null, null, null, null, null, null, null, null, null)
         ex_b = lib.nnop_fa_bwd_ex(C.byref(d), op, *([null] * 13), null, 0, null)
@@ -162,20 +144,20 @@ def test_sinks_null_is_the_ex_call(pkg):
 ])
 def test_bad_descriptor_reports_its_own_code_first(pkg, kw, status):
     lib = pkg._lib.load()
-    st = _sinks_calls(lib, _desc(pkg, **kw), _opts(pkg, reserved=[1]), 0x1001, None)
+    st = _sinks_calls(lib, fa_desc(pkg, **kw), fa_opts(pkg, reserved=[1]), 0x1001, None)
     assert st == (getattr(pkg._lib, status),) * 2
 
 
 def test_reserved_options_are_rejected(pkg):
     lib = pkg._lib.load()
-    assert _sinks_calls(lib, _desc(pkg), _opts(pkg, reserved=[0, 2]), 0x1001, None) == (pkg._lib.NNOP_ERR_OPTS,) * 2
-    assert _sinks_calls(lib, _desc(pkg), _opts(pkg, left=-3), 0x1000, 0x2000) == (pkg._lib.NNOP_ERR_OPTS,) * 2
+    assert _sinks_calls(lib, fa_desc(pkg), fa_opts(pkg, reserved=[0, 2]), 0x1001, None) == (pkg._lib.NNOP_ERR_OPTS,) * 2
+    assert _sinks_calls(lib, fa_desc(pkg), fa_opts(pkg, left=-3), 0x1000, 0x2000) == (pkg._lib.NNOP_ERR_OPTS,) * 2
 
 
 def test_null_pointers_then_alignment(pkg):
     """every call here fails a check before any launch: the fake (never dereferenced) tensor addresses stay on the host"""
     lib = pkg._lib.load()
-    d = _desc(pkg)
+    d = fa_desc(pkg)
     E = pkg._lib
     # NULL tensors: NNOP_ERR_NULL whatever the sinks are (the NULL check comes before the alignment check)
     assert _sinks_calls(lib, d, None, 0x1001, 0x2001) == (E.NNOP_ERR_NULL, E.NNOP_ERR_NULL)
@@ -192,7 +174,7 @@ def test_workspace_size_is_unchanged_by_construction(pkg):
     """the sink adds no parameter to the workspace queries: the size is the size without sinks, and covers the dsinks partials"""
     lib = pkg._lib.load()
     for kw in (dict(), dict(dtype=pkg._lib.NNOP_F32, emb=8, ql=5, kl=7), dict(ql=4097, qh=64, kh=8)):
-        d = _desc(pkg, **kw)
+        d = fa_desc(pkg, **kw)
         n = lib.nnop_fa_bwd_workspace_bytes(C.byref(d))
         rows = d.batch * d.qh * ((d.ql + 63) // 64 * 64)
         assert n >= 2 * 4 * rows >= 4 * d.batch * d.qh * d.ql
@@ -207,24 +189,8 @@ def test_symbols_are_exported_and_abi_stays_7(pkg):
 
 
 # ---- the Julia shim ---------------------------------------------------------------------------------------------------------
-def _strip_c_comments(src):
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
-def _c_param_count(header, name):
-    m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S)
-    return len([p for p in m.group(1).split(",") if p.strip()])
-
-
-def _jl_ccall_types(shim, name):
-    shim = re.sub(r"#[^\n]*", "", shim)
-    m = re.search(r"ccall\(\(:" + name + r", libnnop\(\)\), Cint,\s*\((.*?)\),\s*\n\s*d,", shim, re.S)
-    assert m, name
-    return [t.strip() for t in m.group(1).split(",") if t.strip()]
-
-
 def test_julia_shim_calls_only_declared_symbols():
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     declared = set(re.findall(r"\b(nnop_[a-z_]+)\s*\(", header))
     shim = open(SHIM).read()
     called = set(re.findall(r"ccall\(\(:(nnop_[a-z_]+)", shim))
@@ -236,6 +202,6 @@ def test_julia_shim_calls_only_declared_symbols():
 
 @pytest.mark.parametrize("name", ["nnop_fa_fwd_sinks", "nnop_fa_bwd_sinks"])
 def test_julia_ccall_argument_tuples_match_the_prototypes(name):
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     shim = open(SHIM).read()
-    assert len(_jl_ccall_types(shim, name)) == _c_param_count(header, name)
+    assert len(jl_ccall_types(shim, name)) == c_param_count(header, name)

@@ -1,4 +1,4 @@
-"""Logit soft-capping on the GPU: parity with the fp64 oracle through tests/softcap_ref.py, the cap combined with pair bias, key
+"""Logit soft-capping on the GPU: parity with the fp64 oracle through tests/attn_ref.py, the cap combined with pair bias, key
 padding, window, sinks and GQA, a realistic cap on sharp scores, exactness (no cap = the call without the argument, repeatability,
 saturation), autograd and sharding.  Semantics: include/nnop_hip.h (nnop_fa_fwd_softcap).  That the cap changes these inputs' results
 by far more than the tolerances used here is checked without a GPU in tests/test_softcap_host.py."""
@@ -6,58 +6,18 @@ import numpy as np
 import pytest
 import torch
 
-import softcap_ref
-from softcap_ref import inputs, softcap_fwd, softcap_grads
-from util import assert_close
-from window_ref import dead_rows, window_keep
+import softcap_cases
+from attn_ref import cap_terms, check_parity, inputs
+from util import to64
 
 pytestmark = pytest.mark.gpu
 
 
-def _np(t):
-    return None if t is None else t.detach().double().cpu().numpy()
-
-
-def _check(pkg, d, dt, causal, cap, window=None, sinks=None, label=""):
-    """the library against softcap_ref, with the gates of test_window_gpu._check (and test_sinks_gpu._check for dsinks)"""
-    q, k, v, do, pair, mask = d["q"], d["k"], d["v"], d["do"], d["pair"], d["mask"]
-    kw = dict(causal=causal, kpad_mask=mask, window=window, sinks=sinks, softcap=cap)
-    o, ms, ls = pkg._flash_attention(q, k, v, pair, **kw)
-    grads = pkg.grad_flash_attention(do, o, ms, ls, q, k, v, pair, **kw)
-    torch.cuda.synchronize()
-    dq, dk, dv, dp = grads[:4]
-    m = None if mask is None else mask.cpu().numpy()
-    rkw = dict(softcap=cap, causal=causal, kpad_mask=m, window=window, sinks=_np(sinks))
-    args = (_np(q), _np(k), _np(v))
-    o_ref, ms_ref, ls_ref = softcap_fwd(*args, _np(pair), **rkw)
-    ref = softcap_grads(*args, _np(do), _np(pair), **rkw)
-    dead = dead_rows(_np(q), _np(k), causal=causal, kpad_mask=m, window=window)
-    if sinks is not None:
-        dead = dead & False                                  # a finite sink: no row is dead
-    live = ~dead
-    assert_close(label + "o", o, o_ref, dt, floor=True)
-    assert np.isneginf(_np(ms)[dead]).all()
-    assert_close(label + "ms", _np(ms)[live], ms_ref[live], dt, floor=True)
-    assert_close(label + "ls", _np(ls)[live], ls_ref[live], dt, 2.0, floor=True)
-    sc = 1.0 if dt == "f32" else 2.0
-    assert (_np(dq)[dead] == 0).all()
-    assert_close(label + "dq", dq, ref[0], dt, sc, floor=True, kind="grad")
-    assert_close(label + "dk", dk, ref[1], dt, sc, floor=True, kind="grad")
-    assert_close(label + "dv", dv, ref[2], dt, sc, floor=True, kind="grad")
-    if pair is not None:
-        assert_close(label + "dpair", dp, ref[3], dt, sc, floor=True, kind="grad")
-        outside = ~window_keep(q.shape[2], k.shape[2], window, causal).T          # [KL, QL]
-        assert (_np(dp)[:, outside, :] == 0).all()
-    if sinks is not None:
-        assert_close(label + "dsinks", grads[4], ref[4], dt, sc, floor=True, kind="grad")
-    return (o, ms, ls) + tuple(grads)
-
-
 # ---- parity grid ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", softcap_ref.parity_grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-cap{}".format(*c))
+@pytest.mark.parametrize("case", softcap_cases.parity_grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-cap{}".format(*c))
 def test_softcap_parity(pkg, dev, case):
     dt, E, causal, QL, KL, cap = case
-    _check(pkg, softcap_ref.grid_inputs(case, dev), dt, causal, cap)
+    check_parity(pkg, softcap_cases.grid_inputs(case, dev), dt, causal, softcap=cap)
 
 
 # ---- combinations (E = 64, 517 x 517) ---------------------------------------------------------------------------------------------
@@ -69,10 +29,10 @@ def test_cap_with_pair_bias(pkg, dev, dt):
     """dpair = dS: against the reference, and NOT scaled by the tanh derivative.  At q x 64 most scores sit at +-c, where
     1 - tanh^2 is ~0: a dpair that went through it would be ~0 where the true one is largest."""
     d = inputs(("pair", dt), 1, 2, 1, 517, 517, 64, dt, dev, pair=True)
-    _check(pkg, d, dt, False, 1.0)
+    check_parity(pkg, d, dt, False, softcap=1.0)
     d["q"] = d["q"] * 64.0
-    dp = _np(_check(pkg, d, dt, False, 1.0, label="saturated ")[6])
-    _, t, _ = softcap_ref._terms(_np(d["q"]), _np(d["k"]), 1.0)
+    dp = to64(check_parity(pkg, d, dt, False, softcap=1.0, label="saturated ")[6])
+    _, t, _ = cap_terms(to64(d["q"]), to64(d["k"]), 1.0)
     wrong = dp * np.transpose(1.0 - t * t, (0, 3, 2, 1))
     assert np.abs(dp - wrong).max() > 0.5 * np.abs(dp).max()
 
@@ -84,14 +44,14 @@ def test_cap_with_key_padding_and_dead_rows(pkg, dev, dt):
     mask[0, :5] = False                                       # under the causal rule rows 0 .. 4 see no key
     mask[0, 400:] = False
     d["mask"] = mask.to(dev)
-    o = _check(pkg, d, dt, True, 2.0)[0]
+    o = check_parity(pkg, d, dt, True, softcap=2.0)[0]
     assert torch.isnan(o[:, :, :5]).all() and torch.isfinite(o[:, :, 5:]).all()
 
 
 @pytest.mark.parametrize("dt", COMBO_DT)
 def test_cap_with_window(pkg, dev, dt):
     d = inputs(("win", dt), 1, 2, 1, 517, 517, 64, dt, dev)
-    _check(pkg, d, dt, False, 1.0, window=(100, 37))
+    check_parity(pkg, d, dt, False, softcap=1.0, window=(100, 37))
 
 
 @pytest.mark.parametrize("dt", COMBO_DT)
@@ -99,19 +59,19 @@ def test_cap_with_sinks(pkg, dev, dt):
     """the sink is not capped: sinks of 3 and -2 under a cap of 1 (a capped sink could never exceed 1)"""
     d = inputs(("sinks", dt), 1, 2, 1, 517, 517, 64, dt, dev)
     sinks = torch.tensor([3.0, -2.0], device=dev)
-    _check(pkg, d, dt, True, 1.0, sinks=sinks)
+    check_parity(pkg, d, dt, True, softcap=1.0, sinks=sinks)
 
 
 @pytest.mark.parametrize("dt", COMBO_DT)
 def test_cap_with_causal_pair_and_padding(pkg, dev, dt):
     d = inputs(("all", dt), 1, 2, 1, 517, 517, 64, dt, dev, pair=True, pad=True)
-    _check(pkg, d, dt, True, 0.5)
+    check_parity(pkg, d, dt, True, softcap=0.5)
 
 
 @pytest.mark.parametrize("dt", COMBO_DT)
 def test_cap_with_gqa(pkg, dev, dt):
     d = inputs(("gqa", dt), 1, 4, 1, 517, 517, 64, dt, dev)
-    _check(pkg, d, dt, True, 2.0)
+    check_parity(pkg, d, dt, True, softcap=2.0)
 
 
 @pytest.mark.parametrize("dt", ["f16", "f32"])
@@ -119,15 +79,15 @@ def test_cap_with_pair_on_the_plain_hip_and_e128_kernels(pkg, dev, dt):
     """the pair-bias bodies that the E = 64 cases above do not run: E = 128 (32-key tiles) and E = 8 (plain HIP)"""
     for E in (128, 8):
         d = inputs(("pair", dt, E), 1, 2, 1, 160, 130, E, dt, dev, pair=True)
-        _check(pkg, d, dt, True, 1.0, window=(64, -1), label=f"E{E} ")
+        check_parity(pkg, d, dt, True, softcap=1.0, window=(64, -1), label=f"E{E} ")
 
 
 # ---- realistic cap ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", softcap_ref.REALISTIC, ids=lambda c: "{}-E{}-L{}x{}-cap{}".format(*c))
+@pytest.mark.parametrize("case", softcap_cases.REALISTIC, ids=lambda c: "{}-E{}-L{}x{}-cap{}".format(*c))
 def test_realistic_cap_on_sharp_scores(pkg, dev, case):
     """c = 30 (Grok-1) on scores of std 8"""
     dt, E, QL, KL, cap = case
-    _check(pkg, softcap_ref.realistic_inputs(case, dev), dt, False, cap)
+    check_parity(pkg, softcap_cases.realistic_inputs(case, dev), dt, False, softcap=cap)
 
 
 # ---- exactness ---------------------------------------------------------------------------------------------------------------------
@@ -171,7 +131,7 @@ def test_capped_runs_are_repeatable(pkg, dev, dt, E, causal, pad):
 def test_saturated_cap_is_finite_and_right(pkg, dev, dt, E):
     """q x 64 under c = 1: every score sits at +-c; no inf or NaN comes out of the tanh"""
     d = inputs(("sat", dt, E), 1, 2, 1, 300, 333, E, dt, dev, qscale=64.0)
-    out = _check(pkg, d, dt, True, 1.0)
+    out = check_parity(pkg, d, dt, True, softcap=1.0)
     for t in out[:6]:
         assert torch.isfinite(t).all()
 

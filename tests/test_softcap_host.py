@@ -1,21 +1,16 @@
-"""CPU tests of logit soft-capping: the reference (tests/softcap_ref.py) against torch fp64 autograd, that the cap changes the results
+"""CPU tests of logit soft-capping: the reference (tests/attn_ref.py) against torch fp64 autograd, that the cap changes the results
 of the GPU tests' inputs by far more than the parity tolerance, the exports and the unchanged ABI, the validation order of
 nnop_fa_fwd_softcap / nnop_fa_bwd_softcap, the kernel-form rules, the Julia shim and the Python argument checks."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-import softcap_ref
-from softcap_ref import softcap_fwd, softcap_grads
-from window_ref import window_fwd, window_keep
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "nnop_hip.h")
-SHIM = os.path.join(ROOT, "nnop.jl_amd", "julia", "NNopHIPExt.jl")
+import softcap_cases
+from abi_util import HEADER, SHIM, c_params, fa_desc, fa_opts, jl_ccall_types, strip_c_comments
+from attn_ref import attention_fwd, attention_grads, window_keep
 
 
 # ---- the reference against torch autograd ----------------------------------------------------------------------------------------
@@ -51,8 +46,8 @@ def test_reference_matches_torch_autograd(c, sinks):
     window = (5, 0) if sinks else None
     sk = np.array([0.3, -1.0, 2.0, 0.0]) if sinks else None
     kw = dict(softcap=c, causal=True, kpad_mask=mask, window=window, sinks=sk)
-    o, ms, ls = softcap_fwd(q, k, v, pair, **kw)
-    grads = softcap_grads(q, k, v, do, pair, **kw)
+    o, ms, ls = attention_fwd(q, k, v, pair, **kw)
+    grads = attention_grads(q, k, v, do, pair, **kw)
 
     t = lambda x: torch.tensor(x, dtype=torch.float64, requires_grad=True)
     tq, tk, tv, tp = t(q), t(k), t(v), t(pair)
@@ -78,7 +73,7 @@ def test_dpair_is_not_scaled_by_the_tanh_derivative():
     rng = np.random.default_rng(3)
     q, k, v, do = (rng.standard_normal((1, 2, 6, 4)) for _ in range(4))
     pair = rng.standard_normal((1, 6, 6, 2))
-    dq, dk, dv, dp = softcap_grads(q * 400.0, k, v, do, pair, softcap=0.5, causal=False)
+    dq, dk, dv, dp = attention_grads(q * 400.0, k, v, do, pair, softcap=0.5, causal=False)
     # (every |s| / c of these inputs is > 6: 1 - tanh^2 < 4 exp(-12) = 2.5e-5 of the O(1) terms dpair keeps)
     assert np.abs(dp).max() > 0.1 and np.abs(dq).max() < 1e-4 * np.abs(dp).max() and np.abs(dk).max() < 1e-2 * np.abs(dp).max()
 
@@ -88,24 +83,31 @@ def test_dead_rows_keep_their_convention():
     q, k, v, do = (rng.standard_normal((1, 2, 6, 4)) for _ in range(4))
     mask = np.ones((1, 6), bool)
     mask[0, :2] = False                                        # causal rows 0, 1 see no key
-    o, ms, ls = softcap_fwd(q, k, v, softcap=1.0, causal=True, kpad_mask=mask)
-    dq = softcap_grads(q, k, v, do, softcap=1.0, causal=True, kpad_mask=mask)[0]
+    o, ms, ls = attention_fwd(q, k, v, softcap=1.0, causal=True, kpad_mask=mask)
+    dq = attention_grads(q, k, v, do, softcap=1.0, causal=True, kpad_mask=mask)[0]
     assert np.isnan(o[:, :, :2]).all() and np.isneginf(ms[:, :, :2]).all() and (dq[:, :, :2] == 0).all()
     assert np.isfinite(o[:, :, 2:]).all()
+    # sinks: head 0 has none (sigma = -inf), so its rows 0, 1 stay dead; head 1's see their sink alone
+    sinks = np.array([-np.inf, 0.5])
+    o, ms, ls = attention_fwd(q, k, v, softcap=1.0, causal=True, kpad_mask=mask, sinks=sinks)
+    grads = attention_grads(q, k, v, do, softcap=1.0, causal=True, kpad_mask=mask, sinks=sinks)
+    assert np.isnan(o[:, 0, :2]).all() and np.isneginf(ms[:, 0, :2]).all() and (o[:, 1, :2] == 0).all() and (ms[:, 1, :2] == 0.5).all()
+    assert all(np.isfinite(g).all() for g in grads if g is not None)
+    assert (grads[0][:, :, :2] == 0).all() and grads[4][0] == 0 and grads[4][1] != 0
 
 
 # ---- the cap must bite: a kernel that ignores it cannot pass the GPU tests ---------------------------------------------------------
 def _bite(d, causal, cap):
     n = lambda t: t.double().numpy()
-    o_c = softcap_fwd(n(d["q"]), n(d["k"]), n(d["v"]), softcap=cap, causal=causal)[0]
-    o_u = window_fwd(n(d["q"]), n(d["k"]), n(d["v"]), causal=causal, window=None)[0]
+    o_c = attention_fwd(n(d["q"]), n(d["k"]), n(d["v"]), softcap=cap, causal=causal)[0]
+    o_u = attention_fwd(n(d["q"]), n(d["k"]), n(d["v"]), causal=causal)[0]
     return np.abs(o_c - o_u).max() / np.abs(o_u).max()
 
 
-@pytest.mark.parametrize("case", softcap_ref.parity_grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-cap{}".format(*c))
+@pytest.mark.parametrize("case", softcap_cases.parity_grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-cap{}".format(*c))
 def test_the_cap_changes_the_grid_inputs_results(case):
     dt, E, causal, QL, KL, cap = case
-    bite = _bite(softcap_ref.grid_inputs(case, "cpu"), causal, cap)
+    bite = _bite(softcap_cases.grid_inputs(case, "cpu"), causal, cap)
     if causal and QL == 1:
         # the one row sees the one key 0: P = 1 whatever its logit, so no cap can show (the case stays in the grid for the kernels'
         # single-row, single-key path; the same lengths meet causal = False at other E, checked below)
@@ -114,29 +116,25 @@ def test_the_cap_changes_the_grid_inputs_results(case):
         assert bite > 0.05
 
 
-@pytest.mark.parametrize("case", softcap_ref.REALISTIC, ids=lambda c: "{}-E{}-L{}x{}-cap{}".format(*c))
+@pytest.mark.parametrize("case", softcap_cases.REALISTIC, ids=lambda c: "{}-E{}-L{}x{}-cap{}".format(*c))
 def test_the_realistic_cap_changes_its_inputs_results(case):
-    assert _bite(softcap_ref.realistic_inputs(case, "cpu"), False, case[4]) > 0.05
+    assert _bite(softcap_cases.realistic_inputs(case, "cpu"), False, case[4]) > 0.05
 
 
 def test_grid_covers_what_it_should():
-    g = softcap_ref.parity_grid()
-    for E in softcap_ref.EMBS:
+    g = softcap_cases.parity_grid()
+    for E in softcap_cases.EMBS:
         sub = [c for c in g if c[1] == E]
-        assert {c[0] for c in sub} == set(softcap_ref.DTYPES) and {c[2] for c in sub} == {False, True}
-        assert {(c[0], c[2]) for c in sub} == {(dt, cz) for dt in softcap_ref.DTYPES for cz in (False, True)}
-    assert {c[5] for c in g} == set(softcap_ref.CAPS)
-    assert {(c[3], c[4]) for c in g if c[1] < 128} == set(softcap_ref.LENS)
+        assert {c[0] for c in sub} == set(softcap_cases.DTYPES) and {c[2] for c in sub} == {False, True}
+        assert {(c[0], c[2]) for c in sub} == {(dt, cz) for dt in softcap_cases.DTYPES for cz in (False, True)}
+    assert {c[5] for c in g} == set(softcap_cases.CAPS)
+    assert {(c[3], c[4]) for c in g if c[1] < 128} == set(softcap_cases.LENS)
     assert sum(1 for c in g if c[3] == 1 and not c[2]) >= 2
 
 
 # ---- exports, ABI --------------------------------------------------------------------------------------------------------------
-def _strip_c_comments(src):
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
 def test_symbols_are_declared_exported_and_bound(pkg):
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     lib = pkg._lib.load()
     for name in ("nnop_fa_fwd_softcap", "nnop_fa_bwd_softcap"):
         assert re.search(r"\bint " + name + r"\s*\(", header)
@@ -164,19 +162,6 @@ def test_abi_version_and_options_layout_are_unchanged(pkg):
 
 
 # ---- validation (NULL / fake tensors: every call fails a check before any launch) ---------------------------------------------------
-def _desc(pkg, **kw):
-    base = dict(dtype=pkg._lib.NNOP_BF16, emb=64, ql=128, kl=128, qh=4, kh=4, batch=2, causal=0)
-    base.update(kw)
-    return pkg._lib.FaDesc(**base)
-
-
-def _opts(pkg, left=-1, right=-1, reserved=None):
-    o = pkg._lib.FaOpts(window_left=left, window_right=right)
-    for i, r in enumerate(reserved or []):
-        o.reserved[i] = r
-    return o
-
-
 def _fwd(lib, d, opts, cap, sinks=None, tensors=None):
     t = C.c_void_p(tensors) if tensors else C.c_void_p(0)
     op = C.byref(opts) if opts is not None else None
@@ -201,19 +186,19 @@ BAD_CAPS = [-1.0, -1e-30, float("nan"), float("inf"), float("-inf")]
 def test_bad_cap_is_err_opts_before_null_pointers(pkg, cap):
     lib = pkg._lib.load()
     E = pkg._lib
-    assert _both(lib, _desc(pkg), None, cap) == (E.NNOP_ERR_OPTS,) * 2                      # NULL tensors: the cap comes first
-    assert _both(lib, _desc(pkg), _opts(pkg, 3, 0), cap, sinks=0x1001) == (E.NNOP_ERR_OPTS,) * 2   # ... and before alignment
+    assert _both(lib, fa_desc(pkg), None, cap) == (E.NNOP_ERR_OPTS,) * 2                      # NULL tensors: the cap comes first
+    assert _both(lib, fa_desc(pkg), fa_opts(pkg, 3, 0), cap, sinks=0x1001) == (E.NNOP_ERR_OPTS,) * 2   # ... and before alignment
 
 
 def test_zero_and_positive_caps_pass_the_cap_check(pkg):
     lib = pkg._lib.load()
     E = pkg._lib
     for cap in (0.0, -0.0, 1e-30, 0.5, 50.0, 3e38):
-        assert _both(lib, _desc(pkg), None, cap) == (E.NNOP_ERR_NULL,) * 2                  # the next check in line
+        assert _both(lib, fa_desc(pkg), None, cap) == (E.NNOP_ERR_NULL,) * 2                  # the next check in line
     fake = 0x10000
-    assert _fwd(lib, _desc(pkg), None, 30.0, sinks=0x1002, tensors=fake) == E.NNOP_ERR_ALIGN
-    assert _bwd(lib, _desc(pkg), None, 30.0, sinks=0x1000, dsinks=0x2001, tensors=fake) == E.NNOP_ERR_ALIGN
-    assert _bwd(lib, _desc(pkg), None, 30.0, sinks=0x1000, dsinks=None, tensors=fake) == E.NNOP_ERR_NULL
+    assert _fwd(lib, fa_desc(pkg), None, 30.0, sinks=0x1002, tensors=fake) == E.NNOP_ERR_ALIGN
+    assert _bwd(lib, fa_desc(pkg), None, 30.0, sinks=0x1000, dsinks=0x2001, tensors=fake) == E.NNOP_ERR_ALIGN
+    assert _bwd(lib, fa_desc(pkg), None, 30.0, sinks=0x1000, dsinks=None, tensors=fake) == E.NNOP_ERR_NULL
 
 
 @pytest.mark.parametrize("kw,status", [
@@ -226,19 +211,19 @@ def test_descriptor_then_options_then_cap(pkg, kw, status):
     lib = pkg._lib.load()
     E = pkg._lib
     # a bad descriptor reports its own code whatever the options and the cap are
-    assert _both(lib, _desc(pkg, **kw), _opts(pkg, reserved=[1]), -1.0) == (getattr(E, status),) * 2
+    assert _both(lib, fa_desc(pkg, **kw), fa_opts(pkg, reserved=[1]), -1.0) == (getattr(E, status),) * 2
     # bad options come before a bad cap: both are NNOP_ERR_OPTS, so tell them apart by fixing one at a time
-    assert _both(lib, _desc(pkg), _opts(pkg, reserved=[0, 2]), 1.0) == (E.NNOP_ERR_OPTS,) * 2
-    assert _both(lib, _desc(pkg), _opts(pkg, left=-3), 1.0) == (E.NNOP_ERR_OPTS,) * 2
-    assert _both(lib, _desc(pkg), _opts(pkg, reserved=[0, 2]), float("nan")) == (E.NNOP_ERR_OPTS,) * 2
-    assert _both(lib, _desc(pkg), _opts(pkg), 1.0) == (E.NNOP_ERR_NULL,) * 2
+    assert _both(lib, fa_desc(pkg), fa_opts(pkg, reserved=[0, 2]), 1.0) == (E.NNOP_ERR_OPTS,) * 2
+    assert _both(lib, fa_desc(pkg), fa_opts(pkg, left=-3), 1.0) == (E.NNOP_ERR_OPTS,) * 2
+    assert _both(lib, fa_desc(pkg), fa_opts(pkg, reserved=[0, 2]), float("nan")) == (E.NNOP_ERR_OPTS,) * 2
+    assert _both(lib, fa_desc(pkg), fa_opts(pkg), 1.0) == (E.NNOP_ERR_NULL,) * 2
 
 
 def test_cap_zero_is_the_sinks_call(pkg):
     lib = pkg._lib.load()
     null = C.c_void_p(0)
-    for d, opts in ((_desc(pkg), None), (_desc(pkg), _opts(pkg, 3, 0)), (_desc(pkg, emb_k=32), None),
-                    (_desc(pkg), _opts(pkg, reserved=[1]))):
+    for d, opts in ((fa_desc(pkg), None), (fa_desc(pkg), fa_opts(pkg, 3, 0)), (fa_desc(pkg, emb_k=32), None),
+                    (fa_desc(pkg), fa_opts(pkg, reserved=[1]))):
         op = C.byref(opts) if opts is not None else None
         for sinks in (None, 0x1001):
             sk = C.c_void_p(sinks)
@@ -248,7 +233,7 @@ def test_cap_zero_is_the_sinks_call(pkg):
 
 
 def test_workspace_queries_take_no_cap(pkg):
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     assert re.search(r"size_t nnop_fa_bwd_workspace_bytes\(const nnop_fa_desc\* d\);", header)
     assert re.search(r"size_t nnop_fa_bwd_workspace_bytes_pair\(const nnop_fa_desc\* d\);", header)
 
@@ -260,7 +245,7 @@ def test_capped_problems_run_the_32_row_or_plain_hip_kernels(pkg):
     for dt in (L.NNOP_BF16, L.NNOP_F16):
         for E in (64, 128):
             for causal in (0, 1):
-                d = _desc(pkg, dtype=dt, emb=E, ql=4096, kl=4096, qh=8, kh=8, batch=4, causal=causal)
+                d = fa_desc(pkg, dtype=dt, emb=E, ql=4096, kl=4096, qh=8, kh=8, batch=4, causal=causal)
                 # without a cap this problem runs the duo / w64 forms and the w64 backward: the cap moves it
                 assert lib.nnop_debug_fwd_form_ex(C.byref(d), None, 0, 0) in (2, 4)
                 assert lib.nnop_debug_bwd_form_ex(C.byref(d), None, 0, 0) == 3
@@ -268,12 +253,12 @@ def test_capped_problems_run_the_32_row_or_plain_hip_kernels(pkg):
                     assert lib.nnop_debug_fwd_form_cap(C.byref(d), None, C.c_float(30.0), 0, mask) == 0
                     assert lib.nnop_debug_bwd_form_cap(C.byref(d), None, C.c_float(30.0), 0, mask) == 0
                 assert lib.nnop_debug_fwd_form_cap(C.byref(d), None, C.c_float(30.0), 1, 0) == 0
-    d8 = _desc(pkg, emb=8)
+    d8 = fa_desc(pkg, emb=8)
     assert lib.nnop_debug_fwd_form_cap(C.byref(d8), None, C.c_float(1.0), 0, 0) == 3
     assert lib.nnop_debug_bwd_form_cap(C.byref(d8), None, C.c_float(1.0), 0, 0) == 0
-    assert pkg._lib.fwd_form(_desc(pkg, ql=4096, kl=4096), softcap=30.0) == "fa_fwd_cap_kernel"
+    assert pkg._lib.fwd_form(fa_desc(pkg, ql=4096, kl=4096), softcap=30.0) == "fa_fwd_cap_kernel"
     assert pkg._lib.fwd_form(d8, softcap=1.0) == "fa_fwd_generic_cap_kernel"
-    assert pkg._lib.bwd_kernels(_desc(pkg, ql=4096, kl=4096), softcap=30.0) == ("fa_bwd_dkdv_kernel", "fa_bwd_dq_kernel")
+    assert pkg._lib.bwd_kernels(fa_desc(pkg, ql=4096, kl=4096), softcap=30.0) == ("fa_bwd_dkdv_kernel", "fa_bwd_dq_kernel")
 
 
 def test_cap_zero_reports_what_ex_reports(pkg):
@@ -281,21 +266,21 @@ def test_cap_zero_reports_what_ex_reports(pkg):
     L = pkg._lib
     for kw in (dict(ql=4096, kl=4096, qh=8, kh=8), dict(emb=128, ql=2048, kl=2048, causal=1), dict(emb=8), dict(dtype=L.NNOP_F32),
                dict(emb=32, ql=2048, kl=2048, qh=8, kh=8, batch=8, causal=1)):
-        d = _desc(pkg, **kw)
-        for opts in (None, _opts(pkg, 100, 0)):
+        d = fa_desc(pkg, **kw)
+        for opts in (None, fa_opts(pkg, 100, 0)):
             op = C.byref(opts) if opts is not None else None
             for pair, mask in ((0, 0), (1, 0), (0, 1)):
                 assert lib.nnop_debug_fwd_form_cap(C.byref(d), op, C.c_float(0.0), pair, mask) == \
                     lib.nnop_debug_fwd_form_ex(C.byref(d), op, pair, mask)
                 assert lib.nnop_debug_bwd_form_cap(C.byref(d), op, C.c_float(0.0), pair, mask) == \
                     lib.nnop_debug_bwd_form_ex(C.byref(d), op, pair, mask)
-    assert lib.nnop_debug_fwd_form_cap(C.byref(_desc(pkg)), None, C.c_float(-1.0), 0, 0) == L.NNOP_ERR_OPTS
-    assert lib.nnop_debug_bwd_form_cap(C.byref(_desc(pkg)), None, C.c_float(float("nan")), 0, 0) == L.NNOP_ERR_OPTS
+    assert lib.nnop_debug_fwd_form_cap(C.byref(fa_desc(pkg)), None, C.c_float(-1.0), 0, 0) == L.NNOP_ERR_OPTS
+    assert lib.nnop_debug_bwd_form_cap(C.byref(fa_desc(pkg)), None, C.c_float(float("nan")), 0, 0) == L.NNOP_ERR_OPTS
 
 
 # ---- the Julia shim ---------------------------------------------------------------------------------------------------------
 def test_julia_shim_has_the_function_its_rule_and_both_calls():
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     shim = open(SHIM).read()
     called = set(re.findall(r"ccall\(\(:(nnop_[a-z_]+)", shim))
     assert {"nnop_fa_fwd_softcap", "nnop_fa_bwd_softcap"} <= called
@@ -310,13 +295,8 @@ def test_julia_shim_has_the_function_its_rule_and_both_calls():
 
 @pytest.mark.parametrize("name", ["nnop_fa_fwd_softcap", "nnop_fa_bwd_softcap"])
 def test_julia_ccall_argument_tuples_match_the_prototypes(name):
-    header = _strip_c_comments(open(HEADER).read())
-    shim = re.sub(r"#[^\n]*", "", open(SHIM).read())
-    m = re.search(r"ccall\(\(:" + name + r", libnnop\(\)\), Cint,\s*\((.*?)\),\s*\n\s*d,", shim, re.S)
-    assert m, name
-    types = [t.strip() for t in m.group(1).split(",") if t.strip()]
-    proto = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S).group(1)
-    params = [p.strip() for p in proto.split(",") if p.strip()]
+    types = jl_ccall_types(open(SHIM).read(), name)
+    params = c_params(strip_c_comments(open(HEADER).read()), name)
     assert len(types) == len(params)
     assert [i for i, t in enumerate(types) if t == "Cfloat"] == [i for i, p in enumerate(params) if p.startswith("float softcap")]
 

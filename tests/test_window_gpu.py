@@ -1,13 +1,9 @@
-"""Sliding-window (local) attention on the GPU: parity with the fp64 oracle under a 0 / -inf window bias (tests/window_ref.py),
+"""Sliding-window (local) attention on the GPU: parity with the fp64 oracle under a 0 / -inf window bias (tests/attn_ref.py),
 exact and normalised windows, repeatability, autograd and sharding.  Window semantics: include/nnop_hip.h (nnop_fa_opts)."""
-import zlib
-
-import numpy as np
 import pytest
 import torch
 
-from util import TORCH_DT, assert_close
-from window_ref import dead_rows, window_fwd, window_grads
+from attn_ref import check_parity, inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -64,55 +60,11 @@ def _wide_grid():
     return out
 
 
-def _inputs(key, B, QH, KH, QL, KL, E, dt, dev, pair=False, pad=False):
-    rng = np.random.default_rng(zlib.crc32(repr(key).encode()))
-    mk = lambda *s: torch.tensor(rng.standard_normal(s).astype(np.float32)).to(torch.bfloat16).to(TORCH_DT[dt]).to(dev)
-    d = dict(q=mk(B, QH, QL, E), k=mk(B, KH, KL, E), v=mk(B, KH, KL, E), do=mk(B, QH, QL, E))
-    d["pair"] = mk(B, KL, QL, QH) if pair else None
-    d["mask"] = None
-    if pad:
-        lens = rng.integers(max(1, KL // 3), KL + 1, size=B)
-        d["mask"] = torch.tensor(np.arange(KL)[None, :] < lens[:, None]).to(dev)
-    return d
-
-
-def _np(t):
-    return None if t is None else t.detach().double().cpu().numpy()
-
-
-def _check(pkg, d, dt, causal, window):
-    q, k, v, do, pair, mask = d["q"], d["k"], d["v"], d["do"], d["pair"], d["mask"]
-    o, ms, ls = pkg._flash_attention(q, k, v, pair, causal=causal, kpad_mask=mask, window=window)
-    dq, dk, dv, dp = pkg.grad_flash_attention(do, o, ms, ls, q, k, v, pair, causal=causal, kpad_mask=mask, window=window)
-    torch.cuda.synchronize()
-    m = None if mask is None else mask.cpu().numpy()
-    args = (_np(q), _np(k), _np(v))
-    o_ref, ms_ref, ls_ref = window_fwd(*args, _np(pair), causal=causal, kpad_mask=m, window=window)
-    dead = dead_rows(_np(q), _np(k), causal=causal, kpad_mask=m, window=window)
-    assert_close("o", o, o_ref, dt, floor=True)
-    live = ~dead
-    assert np.isneginf(_np(ms)[dead]).all()
-    assert_close("ms", _np(ms)[live], ms_ref[live], dt, floor=True)
-    assert_close("ls", _np(ls)[live], ls_ref[live], dt, 2.0, floor=True)
-    rq, rk, rv, rp = window_grads(*args, _np(do), _np(pair), causal=causal, kpad_mask=m, window=window)
-    sc = 1.0 if dt == "f32" else 2.0
-    assert (_np(dq)[dead] == 0).all()
-    assert_close("dq", dq, rq, dt, sc, floor=True, kind="grad")
-    assert_close("dk", dk, rk, dt, sc, floor=True, kind="grad")
-    assert_close("dv", dv, rv, dt, sc, floor=True, kind="grad")
-    if pair is not None:
-        assert_close("dpair", dp, rp, dt, sc, floor=True, kind="grad")
-        B, QH, QL, _ = q.shape
-        from window_ref import window_keep
-        outside = ~window_keep(QL, k.shape[2], window, causal).T          # [KL, QL]
-        assert (_np(dp)[:, outside, :] == 0).all()
-
-
 @pytest.mark.parametrize("case", _grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-w{}_{}".format(*c[:5], *c[5]))
 def test_window_parity(pkg, dev, case):
     dt, E, causal, QL, KL, window = case
-    d = _inputs(case, 1, 2, 1, QL, KL, E, dt, dev)
-    _check(pkg, d, dt, causal, window)
+    d = inputs(case, 1, 2, 1, QL, KL, E, dt, dev)
+    check_parity(pkg, d, dt, causal, window=window)
 
 
 def test_grids_stay_windowed():
@@ -123,8 +75,8 @@ def test_grids_stay_windowed():
 @pytest.mark.parametrize("case", _wide_grid(), ids=lambda c: "{}-E{}-c{}-L{}x{}-w{}_{}".format(*c[:5], *c[5]))
 def test_window_parity_wide(pkg, dev, case):
     dt, E, causal, QL, KL, window = case
-    d = _inputs(("wide",) + case, 1, 2, 1, QL, KL, E, dt, dev, pad=True)
-    _check(pkg, d, dt, causal, window)
+    d = inputs(("wide",) + case, 1, 2, 1, QL, KL, E, dt, dev, pad=True)
+    check_parity(pkg, d, dt, causal, window=window)
 
 
 @pytest.mark.parametrize("dt", DTYPES)
@@ -136,8 +88,8 @@ def test_window_parity_wide(pkg, dev, case):
 ])
 def test_window_parity_gqa_padding_pair(pkg, dev, dt, E, QL, KL, causal, window, pair, pad):
     QH, KH = (8, 2) if not pair else (2, 2)
-    d = _inputs((dt, E, QL, KL, window), 2, QH, KH, QL, KL, E, dt, dev, pair=pair, pad=pad)
-    _check(pkg, d, dt, causal, window)
+    d = inputs((dt, E, QL, KL, window), 2, QH, KH, QL, KL, E, dt, dev, pair=pair, pad=pad)
+    check_parity(pkg, d, dt, causal, window=window)
 
 
 @pytest.mark.parametrize("dt", DTYPES)
@@ -145,7 +97,7 @@ def test_window_parity_gqa_padding_pair(pkg, dev, dt, E, QL, KL, causal, window,
 def test_window_zero_is_exact(pkg, dev, dt, E):
     """window (0, 0): query i sees key i alone -> o = v[i] bitwise, ls = 1 (logits kept tiny so that exp(s - max) is 1 exactly)"""
     B, QH, KH, QL, KL = 2, 4, 2, 200, 260
-    d = _inputs(("exact", dt, E), B, QH, KH, QL, KL, E, dt, dev)
+    d = inputs(("exact", dt, E), B, QH, KH, QL, KL, E, dt, dev)
     q = d["q"] * 2.0 ** -12
     o, ms, ls = pkg._flash_attention(q, d["k"], d["v"], causal=False, window=(0, 0))
     torch.cuda.synchronize()
@@ -171,7 +123,7 @@ NORM_SHAPES = [
 def test_windows_that_normalise_away_are_bitwise_the_unwindowed_call(pkg, dev, shape):
     dt, E, QL, KL, QH, KH, B, causal = shape[:8]
     pair = len(shape) > 8
-    d = _inputs(shape, B, QH, KH, QL, KL, E, dt, dev, pair=pair)
+    d = inputs(shape, B, QH, KH, QL, KL, E, dt, dev, pair=pair)
     q, k, v, do, p = d["q"], d["k"], d["v"], d["do"], d["pair"]
     ref_f = pkg._flash_attention(q, k, v, p, causal=causal)
     ref_b = pkg.grad_flash_attention(do, *ref_f, q, k, v, p, causal=causal)
@@ -191,7 +143,7 @@ def test_windows_that_normalise_away_are_bitwise_the_unwindowed_call(pkg, dev, s
     ("f16", 16, False, (-1, 5), False),
 ])
 def test_windowed_runs_are_repeatable(pkg, dev, dt, E, causal, window, pad):
-    d = _inputs(("rep", dt, E), 2, 4, 2, 700, 650, E, dt, dev, pad=pad)
+    d = inputs(("rep", dt, E), 2, 4, 2, 700, 650, E, dt, dev, pad=pad)
     runs = []
     for _ in range(2):
         o, ms, ls = pkg._flash_attention(d["q"], d["k"], d["v"], causal=causal, kpad_mask=d["mask"], window=window)
@@ -202,7 +154,7 @@ def test_windowed_runs_are_repeatable(pkg, dev, dt, E, causal, window, pad):
 
 
 def test_autograd_matches_grad_flash_attention(pkg, dev):
-    d = _inputs("autograd", 2, 4, 2, 333, 333, 64, "bf16", dev, pair=True)
+    d = inputs("autograd", 2, 4, 2, 333, 333, 64, "bf16", dev, pair=True)
     window = (50, 10)
     leaves = [d[n].clone().requires_grad_(True) for n in ("q", "k", "v", "pair")]
     o = pkg.flash_attention(*leaves, causal=True, window=window)
@@ -218,7 +170,7 @@ def test_autograd_matches_grad_flash_attention(pkg, dev):
 def test_sharded_window_is_bitwise_the_unsharded_call(pkg, dev, world):
     from importlib import import_module
     shard = import_module(pkg.__name__ + ".shard")
-    d = _inputs(("shard", world), 3, 4, 2, 400, 400, 64, "bf16", dev)
+    d = inputs(("shard", world), 3, 4, 2, 400, 400, 64, "bf16", dev)
     q, k, v, do = d["q"], d["k"], d["v"], d["do"]
     window = (90, 0)
     o, ms, ls = pkg._flash_attention(q, k, v, causal=True, window=window)

@@ -1,30 +1,13 @@
 """CPU tests of the sliding-window boundary (ABI version 7): option validation of nnop_fa_fwd_ex / nnop_fa_bwd_ex, the kernel forms a
 window selects (no device needed), the window reference against an explicit loop, and the Julia shim's declarations."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-from window_ref import window_bias, window_fwd, window_grads, window_keep
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "nnop_hip.h")
-SHIM = os.path.join(ROOT, "nnop.jl_amd", "julia", "NNopHIPExt.jl")
-
-
-def _desc(pkg, **kw):
-    base = dict(dtype=pkg._lib.NNOP_BF16, emb=64, ql=128, kl=128, qh=4, kh=4, batch=2, causal=0)
-    base.update(kw)
-    return pkg._lib.FaDesc(**base)
-
-
-def _opts(pkg, left=-1, right=-1, reserved=None):
-    o = pkg._lib.FaOpts(window_left=left, window_right=right)
-    for i, r in enumerate(reserved or []):
-        o.reserved[i] = r
-    return o
+from abi_util import HEADER, SHIM, fa_desc, fa_opts, strip_c_comments
+from attn_ref import attention_fwd, attention_grads, window_bias, window_keep
 
 
 def _both(lib, d, opts):
@@ -44,13 +27,13 @@ def _both(lib, d, opts):
 ])
 def test_option_validation_codes(pkg, opts_kw, status):
     lib = pkg._lib.load()
-    st_f, st_b = _both(lib, _desc(pkg), _opts(pkg, **opts_kw))
+    st_f, st_b = _both(lib, fa_desc(pkg), fa_opts(pkg, **opts_kw))
     assert st_f == st_b == getattr(pkg._lib, status)
 
 
 def test_opts_null_is_the_call_without_options(pkg):
     lib = pkg._lib.load()
-    assert _both(lib, _desc(pkg), None) == (pkg._lib.NNOP_ERR_NULL, pkg._lib.NNOP_ERR_NULL)
+    assert _both(lib, fa_desc(pkg), None) == (pkg._lib.NNOP_ERR_NULL, pkg._lib.NNOP_ERR_NULL)
 
 
 @pytest.mark.parametrize("kw,status", [
@@ -61,7 +44,7 @@ def test_opts_null_is_the_call_without_options(pkg):
 ])
 def test_bad_descriptor_reports_its_own_code_before_the_options(pkg, kw, status):
     lib = pkg._lib.load()
-    st_f, st_b = _both(lib, _desc(pkg, **kw), _opts(pkg, left=-2, reserved=[1]))
+    st_f, st_b = _both(lib, fa_desc(pkg, **kw), fa_opts(pkg, left=-2, reserved=[1]))
     assert st_f == st_b == getattr(pkg._lib, status)
 
 
@@ -119,7 +102,7 @@ def test_a_window_that_normalises_away_reports_the_unwindowed_form(pkg, shape):
 
 
 def test_form_hooks_validate_options(pkg):
-    d = _desc(pkg)
+    d = fa_desc(pkg)
     with pytest.raises(ValueError):
         pkg._lib.fwd_form(d, window=(-2, 0))
     with pytest.raises(TypeError):
@@ -168,8 +151,8 @@ def test_window_reference_matches_an_explicit_loop(QL, KL, window, causal):
     kpad = np.ones((B, KL), bool)
     kpad[1, -2:] = False
     o_l, dq_l, dk_l, dv_l = _loop_attention(q, k, v, dO, window, causal, kpad)
-    o, ms, ls = window_fwd(q, k, v, causal=causal, kpad_mask=kpad, window=window)
-    dq, dk, dv, dp = window_grads(q, k, v, dO, causal=causal, kpad_mask=kpad, window=window)
+    o, ms, ls = attention_fwd(q, k, v, causal=causal, kpad_mask=kpad, window=window)
+    dq, dk, dv, dp = attention_grads(q, k, v, dO, causal=causal, kpad_mask=kpad, window=window)
     assert dp is None
     assert (np.isnan(o) == np.isnan(o_l)).all()
     np.testing.assert_allclose(np.nan_to_num(o), np.nan_to_num(o_l), rtol=1e-12, atol=1e-12)
@@ -192,18 +175,14 @@ def test_pair_bias_gradient_is_zero_outside_the_window():
     rng = np.random.default_rng(5)
     q, k, v = rng.standard_normal((1, 2, 9, 8)), rng.standard_normal((1, 2, 9, 8)), rng.standard_normal((1, 2, 9, 8))
     pair, dO = rng.standard_normal((1, 9, 9, 2)), rng.standard_normal((1, 2, 9, 8))
-    dq, dk, dv, dp = window_grads(q, k, v, dO, pair, causal=False, window=(1, 1))
+    dq, dk, dv, dp = attention_grads(q, k, v, dO, pair, causal=False, window=(1, 1))
     outside = ~window_keep(9, 9, (1, 1)).T                   # [KL, QL]
     assert (dp[0][outside] == 0).all() and (dp[0][~outside] != 0).any()
 
 
 # ---- the Julia shim ---------------------------------------------------------------------------------------------------------
-def _strip_c_comments(src):
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-
-
 def test_julia_shim_calls_only_declared_symbols():
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     declared = set(re.findall(r"\b(nnop_[a-z_]+)\s*\(", header))
     shim = open(SHIM).read()
     called = set(re.findall(r"ccall\(\(:(nnop_[a-z_]+)", shim))
@@ -213,7 +192,7 @@ def test_julia_shim_calls_only_declared_symbols():
 
 
 def test_julia_faopts_matches_the_c_struct():
-    header = _strip_c_comments(open(HEADER).read())
+    header = strip_c_comments(open(HEADER).read())
     body = re.search(r"typedef struct nnop_fa_opts \{(.*?)\} nnop_fa_opts;", header, re.S).group(1)
     c_fields = re.findall(r"(int32_t)\s+(\w+)(?:\[(\d+)\])?;", body)
     assert [(n, int(a or 1)) for _, n, a in c_fields] == [("window_left", 1), ("window_right", 1), ("reserved", 6)]
@@ -226,11 +205,11 @@ def test_julia_faopts_matches_the_c_struct():
 def test_python_normalises_windows_like_the_library(pkg):
     """a window that removes no key becomes NO options on the host, so that e.g. the pair-bias backward gets the staged workspace
     of the call without a window"""
-    d = _desc(pkg, ql=100, kl=80, causal=0)
+    d = fa_desc(pkg, ql=100, kl=80, causal=0)
     for w in [(-1, -1), (99, -1), (-1, 79), (500, 500)]:
         assert pkg._lib.fa_opts(w, d) is None, w
     for w in [(98, -1), (-1, 78), (0, 0), (-2, -1)]:
         assert pkg._lib.fa_opts(w, d) is not None, w
-    dc = _desc(pkg, ql=100, kl=80, causal=1)
+    dc = fa_desc(pkg, ql=100, kl=80, causal=1)
     assert pkg._lib.fa_opts((-1, 0), dc) is None and pkg._lib.fa_opts((99, 7), dc) is None
     assert pkg._lib.fa_opts((98, 7), dc) is not None

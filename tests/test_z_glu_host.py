@@ -6,22 +6,21 @@ has the right gradient; and the GPU tests' tolerance is restated as a model that
 The file name sorts behind every existing test file on purpose, as tests/test_residual_addnorm_gpu.py explains."""
 import ctypes as C
 import math
-import os
 import re
 
 import pytest
 import torch
 
 import glu_ref as ref
+from abi_util import HEADER, SHIM, strip_c_comments
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("nnop_glu", "nnop_glu_bwd")
 OK = C.c_void_p(0x7f0000001000)              # never dereferenced: every call in this file returns before a launch
 NULL = C.c_void_p(0)
 
 
 def test_exports(pkg):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nnop_hip.h")).read(), flags=re.S)
+    header = strip_c_comments(open(HEADER).read())
     declared = set(re.findall(r"\b(nnop_[a-z_]+)\s*\(", header))
     lib = pkg._lib.load()
     for name in NEW:
@@ -291,7 +290,7 @@ def test_tolerance_model(act, dt):
 
 # ---- the Julia shim ---------------------------------------------------------------------------------------------------
 def test_shim_source_names_the_symbols():
-    src = open(os.path.join(ROOT, "nnop.jl_amd", "julia", "NNopHIPExt.jl")).read()
+    src = open(SHIM).read()
     for name in NEW:
         assert re.search(r"ccall\(\(:%s\b" % name, src), f"the Julia shim does not ccall {name}"
     assert re.search(r"rrule\(::typeof\(glu\)", src), "no rrule for glu in the shim"

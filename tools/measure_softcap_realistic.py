@@ -2,8 +2,8 @@
 
     python tools/measure_softcap_realistic.py > profiles/r05/softcap_realistic.txt
 
-The inputs are those of tests/test_softcap_gpu.test_realistic_cap_on_sharp_scores (tests/softcap_ref.realistic_inputs) in fp32, bf16
-and fp16; the gates are those of tests/util.assert_close with the scales test_softcap_gpu._check uses.  Per tensor: the worst
+The inputs are those of tests/test_softcap_gpu.test_realistic_cap_on_sharp_scores (tests/softcap_cases.realistic_inputs) in fp32, bf16
+and fp16; the gates are those of tests/util.assert_close with the scales tests/attn_ref.check_parity uses.  Per tensor: the worst
 error / tolerance (> 1 misses the gate) and the number of elements outside.  This is the evidence for keeping that test to fp32:
 in bf16 the `ls` gate is missed by the uncapped call as by the capped one."""
 import os
@@ -16,9 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as ge
-import softcap_ref
+from attn_ref import attention_fwd, attention_grads, inputs
 from util import ATOL_FRAC, RTOL, ABS_FLOOR, GRAD_SCALE
-from window_ref import window_fwd, window_grads
 
 pkg = ge.load_package()
 dev = torch.device("cuda:0")
@@ -38,19 +37,15 @@ def ratio(g, ref, dt, scale, kind="fwd"):
 cases = [(dt, E, 130, 517, 30.0) for dt in ("f32", "bf16") for E in (64, 128)] + [("f16", 64, 130, 517, 30.0)]
 for case in cases:
     dt, E, QL, KL, cap = case
-    d = softcap_ref.inputs(("real",) + tuple(case), 1, 2, 1, QL, KL, E, dt, dev, qscale=8.0)
+    d = inputs(("real",) + tuple(case), 1, 2, 1, QL, KL, E, dt, dev, qscale=8.0)
     q, k, v, do = d["q"], d["k"], d["v"], d["do"]
     for c in (cap, None):
         o, ms, ls = pkg._flash_attention(q, k, v, causal=False, softcap=c)
         dq, dk, dv = pkg.grad_flash_attention(do, o, ms, ls, q, k, v, causal=False, softcap=c)[:3]
         torch.cuda.synchronize()
         a = (np64(q), np64(k), np64(v))
-        if c is None:
-            fr = window_fwd(*a, None, causal=False, window=None)
-            gr = window_grads(*a, np64(do), None, causal=False, window=None)
-        else:
-            fr = softcap_ref.softcap_fwd(*a, None, softcap=c, causal=False)
-            gr = softcap_ref.softcap_grads(*a, np64(do), None, softcap=c, causal=False)
+        fr = attention_fwd(*a, causal=False, softcap=c)
+        gr = attention_grads(*a, np64(do), causal=False, softcap=c)
         sc = 1.0 if dt == "f32" else 2.0
         rows = [("o", o, fr[0], 1.0, "fwd"), ("ms", ms, fr[1], 1.0, "fwd"), ("ls", ls, fr[2], 2.0, "fwd"),
                 ("dq", dq, gr[0], sc, "grad"), ("dk", dk, gr[1], sc, "grad"), ("dv", dv, gr[2], sc, "grad")]
