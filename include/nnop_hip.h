@@ -412,6 +412,48 @@ int nnop_glu_bwd(const nnop_glu_desc* d, void* dgate, void* dup /* NULL iff inte
                  const void* gate, const void* up /* NULL iff interleaved */, nnop_stream_t stream);
 
 /*
+ * Cross-entropy loss over the classes of a row (no counterpart in the reference): the loss over an LM head's logits, forward and
+ * pullback in one pass over memory each.  The forward reads every logit once and writes 8 bytes per row; the pullback reads once and
+ * writes once; nothing of size rows x n is kept in between (the row's log-sum-exp is).  fp32 arithmetic for every element type.
+ * For a row x[0..n) with target t:
+ *   z_j  = x_j, or c tanh(x_j / c) with softcap = c > 0 (Gemma-2's final-logit cap: c = 30)
+ *   lse  = log sum_j exp(z_j),  p_j = exp(z_j - lse)
+ *   loss = (1 - eps) (lse - z_t) + eps (lse - mean_j z_j) + zeta lse^2       eps = label_smoothing (torch's meaning), zeta = z_loss
+ *   dx_j = g [ p_j (1 + 2 zeta lse) - (1 - eps) [j = t] - eps / n ] (1 - (z_j / c)^2)       g = dloss of the row; the last factor is 1
+ *                                                                                           without a cap
+ * Special rows.  Stored target == ignore_index (compared before index_base is subtracted): loss = 0, lse is written, dx = 0 (written).
+ * Any other target outside [0, n) after index_base is subtracted: loss = NaN and the whole dx row is NaN; the bad index is never turned
+ * into an address, no other row is affected, and nothing asserts, traps or synchronises.  -inf logits have p = 0 and gradient 0; a row
+ * that is all -inf gives NaN, a -inf at the target gives +inf loss.
+ * logits : [rows] rows of n elements, ld >= n apart; dlogits likewise with ld_grad; the elements [n, ld_grad) of a dlogits row are never
+ * written.  dlogits may be logits itself (same base, ld_grad == ld): the in-place gradient; any other overlap is undefined.
+ * Every shape and alignment works: rows whose start is not 16-byte aligned (odd ld, an offset base) take element accesses.
+ * Checks, in this order, all before any device work: NNOP_ERR_DTYPE; NNOP_ERR_OPTS for index_bytes not 4 / 8, index_base not 0 / 1, a
+ * reserved field not 0, label_smoothing outside [0, 1], a z_loss or softcap that is NaN, infinite or negative; NNOP_ERR_SHAPE for
+ * rows <= 0, n <= 0, ld < n, ld_grad < n (pullback only), n or rows above 2^31 - 1; NNOP_ERR_NULL; NNOP_ERR_ALIGN for logits / dlogits
+ * not aligned to the element size, loss / lse / dloss to 4 bytes, targets to index_bytes.
+ * No workspace; asynchronous on the stream like every other entry point.
+ */
+typedef struct nnop_xent_desc {
+    int32_t dtype;          /* nnop_dtype of logits and dlogits */
+    int32_t index_bytes;    /* 4 or 8: int32 / int64 targets */
+    int64_t rows, n;        /* tokens, classes */
+    int64_t ld, ld_grad;    /* row strides in elements of logits / dlogits, each >= n (ld_grad is read by _bwd only) */
+    int64_t ignore_index;   /* compared with the stored target value, before index_base is subtracted */
+    int32_t index_base;     /* 0 (C, torch) or 1 (Julia) */
+    int32_t reserved;       /* 0 */
+    float   label_smoothing;/* [0, 1] */
+    float   z_loss;         /* finite, >= 0 */
+    float   softcap;        /* 0 = none, else finite and > 0 */
+    float   reserved_f;     /* 0 */
+} nnop_xent_desc;
+
+int nnop_cross_entropy(const nnop_xent_desc* d, float* loss /* [rows] */, float* lse /* [rows] */, const void* logits,
+                       const void* targets, nnop_stream_t stream);
+int nnop_cross_entropy_bwd(const nnop_xent_desc* d, void* dlogits, const float* dloss /* [rows] */, const float* lse,
+                           const void* logits, const void* targets, nnop_stream_t stream);
+
+/*
  * Sharding over several devices (ABI version 6).  The reference has no multi-GPU code; its (batch, kv-head) slices -- a KV head with its
  * QH / KH query heads -- are independent in forward and backward (src/attention.jl:27-28,33; src/attention_bwd.jl:28-29,34), so a host
  * that owns several devices gives rank g of `world` the contiguous unit range [g U / world, (g+1) U / world), U = batch * kh, units

@@ -3,7 +3,7 @@
 Holds only what the hot path needs: ``csrc/`` (hand-written gfx950 HIP kernels + the C ABI of
 ``include/nnop_hip.h``), the host-side mirror of the reference interface (``attention.py``; ``rope.py`` for the
 Llama rotary embedding applied to q, k right before attention -- SURVEY.md section 8(f) rank 2; ``softmax.py``, ``norms.py``,
-and ``activations.py`` for the MLP's gated activation), the
+``activations.py`` for the MLP's gated activation and ``losses.py`` for the cross-entropy over the LM head's logits), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -18,7 +18,8 @@ from .norms import rms_norm, _rms_norm, grad_rms_norm, layer_norm, _layer_norm, 
 from .norms import (add_rms_norm, _add_rms_norm, grad_add_rms_norm, add_layer_norm, _add_layer_norm,
                     grad_add_layer_norm)
 from .activations import (glu, swiglu, geglu, glu_packed, _glu, grad_glu, grad_glu_packed, glu_into, grad_glu_into)
-from . import _lib, activations, shard, workmodel
+from .losses import cross_entropy, _cross_entropy, grad_cross_entropy
+from . import _lib, activations, losses, shard, workmodel
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -26,5 +27,6 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "rms_norm", "_rms_norm", "grad_rms_norm", "layer_norm", "_layer_norm", "grad_layer_norm",
            "add_rms_norm", "_add_rms_norm", "grad_add_rms_norm", "add_layer_norm", "_add_layer_norm", "grad_add_layer_norm",
            "glu", "swiglu", "geglu", "glu_packed", "_glu", "grad_glu", "grad_glu_packed", "glu_into", "grad_glu_into", "activations",
+           "cross_entropy", "_cross_entropy", "grad_cross_entropy", "losses",
            "shard", "workmodel", "_lib"]
 __version__ = "0.1.0"

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "nnop_add_layer_norm_bwd",
     "nnop_glu",
     "nnop_glu_bwd",
+    "nnop_cross_entropy",
+    "nnop_cross_entropy_bwd",
     "nnop_fa_shards",
     "nnop_shared_memory",
     "nnop_strerror",
@@ -128,6 +130,13 @@ class GluDesc(C.Structure):
     """struct nnop_glu_desc"""
     _fields_ = [("dtype", C.c_int32), ("act", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32),
                 ("rows", C.c_int64), ("n", C.c_int64), ("ld", C.c_int64), ("alpha", C.c_float), ("limit", C.c_float)]
+
+
+class XentDesc(C.Structure):
+    """struct nnop_xent_desc"""
+    _fields_ = [("dtype", C.c_int32), ("index_bytes", C.c_int32), ("rows", C.c_int64), ("n", C.c_int64), ("ld", C.c_int64),
+                ("ld_grad", C.c_int64), ("ignore_index", C.c_int64), ("index_base", C.c_int32), ("reserved", C.c_int32),
+                ("label_smoothing", C.c_float), ("z_loss", C.c_float), ("softcap", C.c_float), ("reserved_f", C.c_float)]
 
 
 class NNopLibraryMissing(ImportError):
@@ -211,6 +220,11 @@ def load():
     lib.nnop_glu.argtypes = [gd, vp, vp, vp, vp]
     lib.nnop_glu_bwd.restype = C.c_int
     lib.nnop_glu_bwd.argtypes = [gd, vp, vp, vp, vp, vp, vp]
+    xd = C.POINTER(XentDesc)
+    lib.nnop_cross_entropy.restype = C.c_int
+    lib.nnop_cross_entropy.argtypes = [xd, vp, vp, vp, vp, vp]
+    lib.nnop_cross_entropy_bwd.restype = C.c_int
+    lib.nnop_cross_entropy_bwd.argtypes = [xd, vp, vp, vp, vp, vp, vp]
     lib.nnop_fa_shards.restype = C.c_int
     lib.nnop_fa_shards.argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int, C.POINTER(FaShard)]
     lib.nnop_shared_memory.restype = C.c_int

@@ -99,6 +99,11 @@ int launch_glu(const nnop_glu_desc& d, void* y, const void* gate, const void* up
 int launch_glu_bwd(const nnop_glu_desc& d, void* dgate, void* dup, const void* dy, const void* gate, const void* up,
                    hipStream_t s);
 
+// xent.hip
+int launch_xent(const nnop_xent_desc& d, float* loss, float* lse, const void* logits, const void* targets, hipStream_t s);
+int launch_xent_bwd(const nnop_xent_desc& d, void* dlogits, const float* dloss, const float* lse, const void* logits,
+                    const void* targets, hipStream_t s);
+
 // Embedding dims the MFMA kernels are instantiated for.
 // MFMA-tiled kernels: 16, 32, 64, 128; every other power of two up to 512: fa_generic.hpp (correctness path)
 inline bool emb_tiled(int e) { return e == 16 || e == 32 || e == 64 || e == 128; }

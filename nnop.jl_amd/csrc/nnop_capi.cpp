@@ -145,10 +145,13 @@ const char* nnop_strerror(int status) {
         case NNOP_ERR_HIP: return "HIP runtime error at kernel launch.";
         case NNOP_ERR_ALIGN:
             return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls "
-                   "and for the arrays of nnop_glu).";
+                   "and for the arrays of nnop_glu; nnop_cross_entropy: the element size for logits and dlogits, 4 bytes for loss, lse and dloss, "
+                   "index_bytes for targets).";
         case NNOP_ERR_OPTS:
             return "Invalid options (attention: a reserved field is not 0, a window side is below -1, or a soft cap is negative or not finite; "
-                   "nnop_glu: an unknown act or layout, or with swiglu_oai an alpha that is not finite or a limit that is not finite and positive).";
+                   "nnop_glu: an unknown act or layout, or with swiglu_oai an alpha that is not finite or a limit that is not finite and positive; "
+                   "nnop_cross_entropy: index_bytes not 4 or 8, index_base not 0 or 1, a reserved field not 0, label_smoothing outside [0, 1], "
+                   "or a z_loss or softcap that is negative or not finite).";
         default: return "unknown nnop status";
     }
 }
@@ -396,6 +399,51 @@ int nnop_glu_bwd(const nnop_glu_desc* d, void* dgate, void* dup, const void* dy,
     const int st = check_glu(d, ptrs, 3, absent, 2);
     if (st != NNOP_OK) return st;
     return launch_glu_bwd(*d, dgate, dup, dy, gate, up, (hipStream_t)stream);
+}
+
+// descriptor (dtype, options, shape), then pointers, then alignment; `elems`: logits / dlogits (element size), `f32s`: loss, lse, dloss
+static int check_xent(const nnop_xent_desc* d, bool bwd, const void* const* elems, int n_elems, const void* const* f32s, int n_f32s,
+                      const void* targets) {
+    if (!d) return NNOP_ERR_NULL;
+    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (d->index_bytes != 4 && d->index_bytes != 8) return NNOP_ERR_OPTS;
+    if (d->index_base != 0 && d->index_base != 1) return NNOP_ERR_OPTS;
+    if (d->reserved != 0 || !(d->reserved_f == 0.f)) return NNOP_ERR_OPTS;
+    if (!(d->label_smoothing >= 0.f && d->label_smoothing <= 1.f)) return NNOP_ERR_OPTS;      // (the comparisons are false for NaN)
+    if (!(d->z_loss >= 0.f && d->z_loss <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
+    if (check_softcap(d->softcap) != NNOP_OK) return NNOP_ERR_OPTS;
+    if (d->rows <= 0 || d->n <= 0 || d->ld < d->n || (bwd && d->ld_grad < d->n)) return NNOP_ERR_SHAPE;
+    if (d->n > 0x7fffffffLL || d->rows > 0x7fffffffLL) return NNOP_ERR_SHAPE;
+    for (int i = 0; i < n_elems; ++i)
+        if (!elems[i]) return NNOP_ERR_NULL;
+    for (int i = 0; i < n_f32s; ++i)
+        if (!f32s[i]) return NNOP_ERR_NULL;
+    if (!targets) return NNOP_ERR_NULL;
+    const size_t ea = d->dtype == NNOP_F32 ? 4 : 2;
+    for (int i = 0; i < n_elems; ++i)
+        if (misaligned(elems[i], ea)) return NNOP_ERR_ALIGN;
+    for (int i = 0; i < n_f32s; ++i)
+        if (misaligned(f32s[i], sizeof(float))) return NNOP_ERR_ALIGN;
+    if (misaligned(targets, (size_t)d->index_bytes)) return NNOP_ERR_ALIGN;
+    return NNOP_OK;
+}
+
+int nnop_cross_entropy(const nnop_xent_desc* d, float* loss, float* lse, const void* logits, const void* targets,
+                       nnop_stream_t stream) {
+    const void* const elems[] = {logits};
+    const void* const f32s[] = {loss, lse};
+    const int st = check_xent(d, false, elems, 1, f32s, 2, targets);
+    if (st != NNOP_OK) return st;
+    return launch_xent(*d, loss, lse, logits, targets, (hipStream_t)stream);
+}
+
+int nnop_cross_entropy_bwd(const nnop_xent_desc* d, void* dlogits, const float* dloss, const float* lse, const void* logits,
+                           const void* targets, nnop_stream_t stream) {
+    const void* const elems[] = {dlogits, logits};
+    const void* const f32s[] = {dloss, lse};
+    const int st = check_xent(d, true, elems, 2, f32s, 2, targets);
+    if (st != NNOP_OK) return st;
+    return launch_xent_bwd(*d, dlogits, dloss, lse, logits, targets, (hipStream_t)stream);
 }
 
 size_t nnop_norm_bwd_workspace_bytes(const nnop_norm_desc* d, int layer_norm) {

@@ -14,6 +14,7 @@
 #   NNop._layer_norm / NNop.∇layer_norm                       src/layer_norm.jl:150-204
 #   add_rms_norm / add_layer_norm (+ _fwd / _bwd, rrules)     the residual add fused into the norms (this library's own)
 #   glu (+ glu_fwd / glu_bwd, rrules)                         gated MLP activations: SwiGLU, GeGLU, gpt-oss (this library's own)
+#   cross_entropy (+ cross_entropy_fwd / _bwd, rrule)         loss over the LM head's logits: cap, z-loss, smoothing (this library's own)
 #
 # `flash_attention` and the ChainRules `rrule` (src/attention_crc.jl:4-31) call these generically, so
 # `NNop.flash_attention(q, k, v; causal)` and `Zygote.gradient` keep working unchanged.
@@ -34,7 +35,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm, glu
+export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm, glu, cross_entropy
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -741,6 +742,63 @@ function NNop.CRC.rrule(::typeof(glu), gu; kw...)
     y = glu_fwd(gu; kw...)
     glu_packed_pullback(Δ) = (NNop.CRC.NoTangent(), glu_bwd(_to_roc(NNop.CRC.unthunk(Δ), y), gu; kw...))
     return y, glu_packed_pullback
+end
+
+
+# ---- cross-entropy over the classes (include/nnop_hip.h: nnop_cross_entropy / nnop_cross_entropy_bwd; no counterpart in the reference) ---
+# logits (n, rows) -- the same memory as the header's [rows][n] -- or a view of the first n rows of a padded (ld, rows) matrix; targets
+# are Julia class indices 1..n (index_base = 1), Int32 or Int64; `ignore_index` is compared with the stored value.  Forward: one pass,
+# per-token losses and log-sum-exp in Float32; pullback: one pass, recomputing the probabilities from lse.
+struct XentDesc
+    dtype::Int32; index_bytes::Int32
+    rows::Int64; n::Int64
+    ld::Int64; ld_grad::Int64
+    ignore_index::Int64
+    index_base::Int32; reserved::Int32
+    label_smoothing::Float32; z_loss::Float32; softcap::Float32; reserved_f::Float32
+end
+xentdesc(x, dx, targets, ignore_index, label_smoothing, z_loss, softcap) =
+    Ref(XentDesc(nnop_dtype(eltype(x)), sizeof(eltype(targets)), size(x, 2), size(x, 1), size(x, 2) == 1 ? size(x, 1) : _ld(x),
+                 size(dx, 2) == 1 ? size(dx, 1) : _ld(dx), ignore_index, 1, 0, label_smoothing, z_loss, softcap, 0f0))
+
+# -> (loss, lse), Float32 vectors of length rows
+function cross_entropy_fwd(logits::RowsOf{T}, targets::ROCVector{I}; ignore_index::Integer = -100, label_smoothing::Real = 0,
+                           z_loss::Real = 0, softcap::Real = 0) where {T <: HipFloat, I <: Union{Int32, Int64}}
+    @assert length(targets) == size(logits, 2)
+    loss = ROCArray{Float32}(undef, size(logits, 2)); lse = similar(loss)
+    d = xentdesc(logits, logits, targets, ignore_index, label_smoothing, z_loss, softcap)
+    ok(GC.@preserve loss lse logits targets ccall((:nnop_cross_entropy, libnnop()), Cint,
+        (Ptr{XentDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(loss), devptr(lse), devptr(logits), devptr(targets), hipstream()))
+    return loss, lse
+end
+
+# dlogits: laid out like a dense matrix by default; it may BE logits (in place)
+function cross_entropy_bwd(Δ::ROCVector{Float32}, lse::ROCVector{Float32}, logits::RowsOf{T}, targets::ROCVector{I};
+                           ignore_index::Integer = -100, label_smoothing::Real = 0, z_loss::Real = 0, softcap::Real = 0,
+                           dlogits::RowsOf{T} = ROCArray{T}(undef, size(logits))) where {T <: HipFloat, I <: Union{Int32, Int64}}
+    @assert length(targets) == length(Δ) == length(lse) == size(logits, 2) && size(dlogits) == size(logits)
+    d = xentdesc(logits, dlogits, targets, ignore_index, label_smoothing, z_loss, softcap)
+    ok(GC.@preserve dlogits Δ lse logits targets ccall((:nnop_cross_entropy_bwd, libnnop()), Cint,
+        (Ptr{XentDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(dlogits), devptr(Δ), devptr(lse), devptr(logits), devptr(targets), hipstream()))
+    return dlogits
+end
+
+"""
+    cross_entropy(logits, targets; ignore_index=-100, label_smoothing=0, z_loss=0, softcap=0) -> loss
+
+Per-token cross-entropy losses (a Float32 vector of length `size(logits, 2)`) of `logits` (n, tokens) against the classes `targets`
+in 1..n; tokens whose target equals `ignore_index` have loss 0 and no gradient.  `softcap = c` caps the logits with `c * tanh(x / c)`
+(Gemma-2: 30), `z_loss` adds `z_loss * lse^2`, `label_smoothing` is PyTorch's.  Reduce with `sum` / `mean` as the trainer needs.
+"""
+cross_entropy(logits, targets; kw...) = cross_entropy_fwd(logits, targets; kw...)[1]
+
+function NNop.CRC.rrule(::typeof(cross_entropy), logits, targets; kw...)
+    loss, lse = cross_entropy_fwd(logits, targets; kw...)
+    cross_entropy_pullback(Δ) = (NNop.CRC.NoTangent(), cross_entropy_bwd(_to_roc(NNop.CRC.unthunk(Δ), loss), lse, logits, targets; kw...),
+                                 NNop.CRC.NoTangent())
+    return loss, cross_entropy_pullback
 end
 
 end # module

@@ -52,3 +52,9 @@ def add_norm_bytes(emb, n, itemsize, bwd=False):
 def glu_bytes(n, rows, itemsize, bwd=False):
     """gated activation y = act(gate) * up: forward reads gate, up and writes y; pullback reads dy, gate, up and writes dgate, dup."""
     return (5 if bwd else 3) * n * rows * itemsize
+
+
+def xent_bytes(n, rows, itemsize, index_bytes=8, bwd=False):
+    """cross-entropy over rows of n logits: forward reads the logits and the targets and writes loss and lse (8 bytes per row);
+    pullback reads the logits, the targets, dloss and lse and writes dlogits."""
+    return (2 if bwd else 1) * n * rows * itemsize + 8 * rows + index_bytes * rows

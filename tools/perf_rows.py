@@ -1,8 +1,9 @@
 """Bandwidth of the row-wise operators (online_softmax; later the norms) vs the HBM roofline.  Dev tool: one JSON line
-per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [glu [--shape=rows,n,dtype,layout ...]] [--cpu]
+per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [glu [--shape=rows,n,dtype,layout ...]] [xent [--shape=rows,n,ld,dtype ...] [--crossover]] [--cpu]
 add_norms: the residual add fused into the norms against the two-call sequence it replaces, one JSON line per operator,
 direction and shape (profiles/add_norm/perf.jsonl is this mode's output).
-glu: the gated MLP activations against the torch sequence they replace (profiles/glu/perf.jsonl)."""
+glu: the gated MLP activations against the torch sequence they replace (profiles/glu/perf.jsonl).
+xent: the cross-entropy loss against F.cross_entropy and its autograd backward (profiles/xent/perf.jsonl)."""
 import json
 import os
 import sys
@@ -261,7 +262,92 @@ def glu():
         sys.exit("fused slower than the torch sequence: " + "; ".join(failed))
 
 
+XENT_SHAPES = [(8192, 32000, None), (8192, 50257, 50304), (8192, 128256, None), (4096, 201088, None), (4096, 262144, None)]
+XENT_OPTS = {"plain": {}, "cap+z+smooth": dict(label_smoothing=0.1, z_loss=1e-4, softcap=30.0)}
+
+
+def _xent_torch(x, t, label_smoothing=0.0, z_loss=0.0, softcap=0.0):
+    """the loss as a trainer writes it, in the dtype of the logits: what the fused call replaces"""
+    z = softcap * torch.tanh(x / softcap) if softcap else x
+    loss = torch.nn.functional.cross_entropy(z, t, label_smoothing=label_smoothing)
+    if z_loss:
+        loss = loss + z_loss * (torch.logsumexp(z, -1) ** 2).mean()
+    return loss
+
+
+def xent():
+    """Cross-entropy against the torch calls it replaces, in the same process and dtype: per shape, option set and direction the fused
+    call (forward: cross_entropy with the mean reduction; backward: grad_cross_entropy into a preallocated gradient) and torch
+    (forward: F.cross_entropy, behind c tanh(x / c) where capped and with the z-loss term where asked; backward: autograd of it, graph
+    kept, backward alone timed), alternating, 5 repeats of timeit() each: median with the min-max spread, algorithmic TB/s from
+    workmodel.xent_bytes, ratio of the medians.  --out=FILE (default profiles/xent/perf.jsonl), --tag=NAME, --shape=rows,n,ld,dtype.
+    A shape of 64 MiB or more where the fused call is not faster than torch with the spreads apart ends the run with a non-zero status
+    after every line is printed.
+    --crossover: instead, the fused calls alone over row lengths around the launch rule's crossover (bf16 and fp32, 256 MiB of logits
+    each), for a library variant under NNOP_LIB_PATH that forces one form; default output profiles/xent/perf_crossover.jsonl."""
+    xent_bytes = pkg.workmodel.xent_bytes
+    sweep = "--crossover" in sys.argv
+    default = os.path.join(ROOT, "profiles", "xent", "perf_crossover.jsonl" if sweep else "perf.jsonl")
+    out = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")] or [default])[0]
+    tag = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--tag=")] or [None])[0]
+    extra = [a.split("=", 1)[1].split(",") for a in sys.argv[1:] if a.startswith("--shape=")]
+    if extra:
+        shapes = [(int(r), int(n), int(ld), dt) for r, n, ld, dt in extra]
+    elif sweep:
+        shapes = [(2 ** 27 // n, n, n, dt) for dt in ("bf16", "f32") for n in (256, 512, 1024, 2048, 4096, 8192, 16384, 32768)]
+    else:
+        shapes = [(r, n, ld or n, dt) for dt in ("bf16", "f32") for r, n, ld in XENT_SHAPES] + [(1048576, 1000, 1000, "bf16")]
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    failed, lines = [], ([l for l in open(out).read().splitlines() if l] if sweep and os.path.exists(out) else [])
+    for rows, n, ld, dt in shapes:
+        isz = torch.empty(0, dtype=DT[dt]).element_size()
+        big = rows * n * isz >= 64 * 2 ** 20
+        buf = torch.empty(rows, ld, device=DEV, dtype=DT[dt])
+        for r0 in range(0, rows, 65536):                     # filled in slabs: no fp32 copy of the whole matrix
+            buf[r0:r0 + 65536] = (4 * torch.randn(min(65536, rows - r0), ld, device=DEV)).to(DT[dt])
+        x = buf[:, :n]
+        t = torch.randint(0, n, (rows,), device=DEV)
+        gr = torch.full((rows,), 1.0 / rows, device=DEV)
+        dx = torch.empty(rows, n, device=DEV, dtype=DT[dt])
+        for name, opts in XENT_OPTS.items():
+            _, lse = pkg._cross_entropy(x, t, **opts)
+            fused_f = lambda: pkg.cross_entropy(x, t, **opts)
+            fused_b = lambda: pkg.grad_cross_entropy(gr, lse, x, t, out=dx, **opts)
+            if not sweep:
+                leaf = x.detach().clone().requires_grad_(True)
+                lt = _xent_torch(leaf, t, **opts)
+                seq_f = lambda: _xent_torch(x, t, **opts)
+                seq_b = lambda: torch.autograd.grad(lt, (leaf,), retain_graph=True)
+            for op, bwd, fused, seq in (("cross_entropy", False, fused_f, None if sweep else seq_f),
+                                        ("grad_cross_entropy", True, fused_b, None if sweep else seq_b)):
+                tf, ts = [], []
+                for _ in range(5):                           # alternate: fused, torch, fused, ...
+                    tf.append(timeit(fused, iters=10))
+                    ts.append(timeit(seq, iters=10) if seq else 0.0)
+                tf.sort(); ts.sort()
+                nb = xent_bytes(n, rows, isz, index_bytes=8, bwd=bwd)
+                d = dict(op=op, opts=name, shape=f"rows{rows} n{n} ld{ld}", dtype=dt, us=round(tf[2], 2), us_min=round(tf[0], 2),
+                         us_max=round(tf[4], 2), bytes=nb, tbps=round(nb / tf[2] / 1e6, 3))
+                if not sweep:
+                    ok = bool(tf[4] < ts[0])                 # faster, and the spreads do not overlap
+                    d.update(torch_us=round(ts[2], 2), torch_min=round(ts[0], 2), torch_max=round(ts[4], 2), ratio=round(tf[2] / ts[2], 3),
+                             gate=(ok if big else None))
+                    if big and not ok:
+                        failed.append(f"{op}[{name}] rows{rows} n{n} {dt}")
+                if tag:
+                    d["tag"] = tag
+                print(json.dumps(d), flush=True)
+                lines.append(json.dumps(d))
+            if not sweep:
+                del lt, leaf
+        with open(out, "w") as f:                            # rewritten after every shape: a run that is cut short keeps what it has
+            f.write("\n".join(lines) + "\n")
+        del buf, x, dx
+    if failed:
+        sys.exit("fused not faster than torch: " + "; ".join(failed))
+
+
 if __name__ == "__main__":
-    which = [a for a in sys.argv[1:] if not a.startswith("--")] or ["softmax"]
+    which =[a for a in sys.argv[1:] if not a.startswith("--")] or ["softmax"]
     for w in which:
         globals()[w]()
