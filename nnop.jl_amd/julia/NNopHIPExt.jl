@@ -15,6 +15,7 @@
 #   add_rms_norm / add_layer_norm (+ _fwd / _bwd, rrules)     the residual add fused into the norms (this library's own)
 #   glu (+ glu_fwd / glu_bwd, rrules)                         gated MLP activations: SwiGLU, GeGLU, gpt-oss (this library's own)
 #   cross_entropy (+ cross_entropy_fwd / _bwd, rrule)         loss over the LM head's logits: cap, z-loss, smoothing (this library's own)
+#   qk_norm_rope (+ qk_norm_rope_fwd / _bwd, rrule)           fused QK-norm + RoPE, from the second library libnnop_hip_ext.so
 #
 # `flash_attention` and the ChainRules `rrule` (src/attention_crc.jl:4-31) call these generically, so
 # `NNop.flash_attention(q, k, v; causal)` and `Zygote.gradient` keep working unchanged.
@@ -35,7 +36,7 @@ module NNopHIPExt
 using AMDGPU
 using NNop
 
-export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm, glu, cross_entropy
+export local_flash_attention, flash_attention_sinks, softcap_flash_attention, add_rms_norm, add_layer_norm, glu, cross_entropy, qk_norm_rope
 
 const LIB = Ref{String}("")
 libnnop() = isempty(LIB[]) ? (LIB[] = get(ENV, "NNOP_HIP_LIB", "libnnop_hip.so")) : LIB[]
@@ -799,6 +800,92 @@ function NNop.CRC.rrule(::typeof(cross_entropy), logits, targets; kw...)
     cross_entropy_pullback(Δ) = (NNop.CRC.NoTangent(), cross_entropy_bwd(_to_roc(NNop.CRC.unthunk(Δ), loss), lse, logits, targets; kw...),
                                  NNop.CRC.NoTangent())
     return loss, cross_entropy_pullback
+end
+
+
+# ---- fused QK-norm + RoPE (include/nnop_hip_ext.h: the SECOND library, libnnop_hip_ext.so; no counterpart in the reference) ------------
+# Operators beyond the NNop drop-in boundary live in a library of their own with its own ABI version.  It is opened once with dlopen
+# and its functions are called through dlsym pointers, so the calls into the two libraries cannot be mixed up; status codes are
+# nnop_status, turned into text by the main library (`ok`).  Point ENV["NNOP_HIP_EXT_LIB"] at libnnop_hip_ext.so.
+import Libdl
+
+const EXT_ABI_VERSION = 1
+const EXT_LIB = Ref{Ptr{Cvoid}}(C_NULL)
+function libnnop_ext()
+    if EXT_LIB[] == C_NULL
+        h = Libdl.dlopen(get(ENV, "NNOP_HIP_EXT_LIB", "libnnop_hip_ext.so"))
+        v = ccall(Libdl.dlsym(h, :nnop_ext_abi_version), Cint, ())
+        v == EXT_ABI_VERSION || error("libnnop_hip_ext has ext-ABI version $v, this extension needs $EXT_ABI_VERSION")
+        EXT_LIB[] = h
+    end
+    return EXT_LIB[]
+end
+
+# struct nnop_qknr_desc (include/nnop_hip_ext.h), 48 bytes
+struct QknrDesc
+    dtype::Int32; w_dtype::Int32; cs_dtype::Int32
+    dim::Int32; seq::Int32; qh::Int32; kh::Int32; batch::Int32
+    eps::Float32; offset::Float32
+    reserved::NTuple{2, Int32}
+end
+function qknrdesc(q::ROCArray{T,4}, k::ROCArray{T,4}, wq::ROCVector{W}, wk::ROCVector{W}, cos::ROCArray{C,3}, sin::ROCArray{C,3},
+                  ϵ, offset) where {T, W, C}
+    head_dim, seq, q_heads, batch = size(q)
+    @assert size(k, 1) == head_dim && size(k, 2) == seq && size(k, 4) == batch
+    @assert length(wq) == length(wk) == head_dim
+    @assert size(cos) == size(sin) == (head_dim, seq, batch)
+    return Ref(QknrDesc(nnop_dtype(T), nnop_dtype(W), nnop_dtype(C), head_dim, seq, q_heads, size(k, 3), batch, ϵ, offset, (Int32(0), Int32(0))))
+end
+
+# q (D, L, QH, B), k (D, L, KH, B), cos / sin (D, L, B), wq / wk (D): the memory of the header's layouts.  q_out may be q, k_out may be k.
+function qk_norm_rope_fwd(q::ROCArray{T,4}, k::ROCArray{T,4}, wq::ROCVector{W}, wk::ROCVector{W}, cos::ROCArray{C,3}, sin::ROCArray{C,3};
+                          ϵ::Float32 = 1f-6, offset::Float32 = 0f0, q_out::ROCArray{T,4} = similar(q),
+                          k_out::ROCArray{T,4} = similar(k)) where {T <: HipFloat, W <: HipFloat, C <: HipFloat}
+    @assert size(q_out) == size(q) && size(k_out) == size(k)
+    d = qknrdesc(q, k, wq, wk, cos, sin, ϵ, offset)
+    ok(GC.@preserve q_out k_out q k wq wk cos sin ccall(Libdl.dlsym(libnnop_ext(), :nnop_qk_norm_rope), Cint,
+        (Ptr{QknrDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        d, devptr(q_out), devptr(k_out), devptr(q), devptr(k), devptr(wq), devptr(wk), devptr(cos), devptr(sin), hipstream()))
+    return q_out, k_out
+end
+
+# (Δq, Δk) -> (dq, dk, dwq, dwk); dwq, dwk Float32, summed over rows in a fixed order.  dq may be Δq, dk may be Δk.
+function qk_norm_rope_bwd(Δq::ROCArray{T,4}, Δk::ROCArray{T,4}, q::ROCArray{T,4}, k::ROCArray{T,4}, wq::ROCVector{W}, wk::ROCVector{W},
+                          cos::ROCArray{C,3}, sin::ROCArray{C,3}; ϵ::Float32 = 1f-6, offset::Float32 = 0f0,
+                          dq::ROCArray{T,4} = similar(q), dk::ROCArray{T,4} = similar(k)) where {T <: HipFloat, W <: HipFloat, C <: HipFloat}
+    @assert size(Δq) == size(dq) == size(q) && size(Δk) == size(dk) == size(k)
+    d = qknrdesc(q, k, wq, wk, cos, sin, ϵ, offset)
+    dwq = ROCArray{Float32}(undef, length(wq)); dwk = similar(dwq)
+    nbytes = ccall(Libdl.dlsym(libnnop_ext(), :nnop_qk_norm_rope_bwd_workspace_bytes), Csize_t, (Ptr{QknrDesc},), d)
+    nbytes == 0 && error("libnnop_hip_ext: invalid qk_norm_rope descriptor")
+    ws = ROCArray{UInt8}(undef, nbytes)
+    ok(GC.@preserve dq dk dwq dwk Δq Δk q k wq wk cos sin ws ccall(Libdl.dlsym(libnnop_ext(), :nnop_qk_norm_rope_bwd), Cint,
+        (Ptr{QknrDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+        d, devptr(dq), devptr(dk), devptr(dwq), devptr(dwk), devptr(Δq), devptr(Δk), devptr(q), devptr(k), devptr(wq), devptr(wk),
+        devptr(cos), devptr(sin), devptr(ws), nbytes, hipstream()))
+    return dq, dk, dwq, dwk
+end
+
+"""
+    qk_norm_rope(q, k, wq, wk; cos, sin, ϵ=1f-6, offset=0f0) -> (q′, k′)
+
+The per-head RMSNorm of Qwen3 / Gemma 3 / OLMo 2 on `q` and `k` (weights `wq`, `wk`, gain `w + offset`), then the Llama rotary embedding,
+in one pass over memory: `llama_rope(rms_norm(q, wq), rms_norm(k, wk); cos, sin)` with the norm per head row and no rounding in between.
+Differentiable in `q`, `k`, `wq`, `wk` through the ChainRules rule below, which keeps only its inputs.
+"""
+qk_norm_rope(q, k, wq, wk; cos, sin, ϵ::Float32 = 1f-6, offset::Float32 = 0f0) = qk_norm_rope_fwd(q, k, wq, wk, cos, sin; ϵ, offset)
+
+function NNop.CRC.rrule(::typeof(qk_norm_rope), q, k, wq, wk; cos, sin, ϵ::Float32 = 1f-6, offset::Float32 = 0f0)
+    q2, k2 = qk_norm_rope_fwd(q, k, wq, wk, cos, sin; ϵ, offset)
+    function qk_norm_rope_pullback(Δ)
+        Δq = Δ[1] isa NNop.CRC.AbstractZero ? fill!(similar(q2), 0) : _to_roc(NNop.CRC.unthunk(Δ[1]), q2)
+        Δk = Δ[2] isa NNop.CRC.AbstractZero ? fill!(similar(k2), 0) : _to_roc(NNop.CRC.unthunk(Δ[2]), k2)
+        dq, dk, dwq, dwk = qk_norm_rope_bwd(Δq, Δk, q, k, wq, wk, cos, sin; ϵ, offset)
+        cast(dw, w) = eltype(w) === Float32 ? dw : eltype(w).(dw)
+        return NNop.CRC.NoTangent(), dq, dk, cast(dwq, wq), cast(dwk, wk)
+    end
+    return (q2, k2), qk_norm_rope_pullback
 end
 
 end # module

@@ -2,7 +2,8 @@
 measured time.  Pure arithmetic on shapes; part of the product so that measurement code never needs the test oracle."""
 from __future__ import annotations
 
-__all__ = ["attention_flops", "attention_bytes", "rope_bytes", "softmax_bytes", "norm_bytes", "add_norm_bytes", "glu_bytes"]
+__all__ = ["attention_flops", "attention_bytes", "rope_bytes", "softmax_bytes", "norm_bytes", "add_norm_bytes", "glu_bytes", "xent_bytes",
+           "qknr_bytes"]
 
 
 def attention_flops(E, QL, KL, QH, B, *, causal: bool, mode: str = "fwd", kv_lens=None):
@@ -58,3 +59,14 @@ def xent_bytes(n, rows, itemsize, index_bytes=8, bwd=False):
     """cross-entropy over rows of n logits: forward reads the logits and the targets and writes loss and lse (8 bytes per row);
     pullback reads the logits, the targets, dloss and lse and writes dlogits."""
     return (2 if bwd else 1) * n * rows * itemsize + 8 * rows + index_bytes * rows
+
+
+def qknr_bytes(D, L, QH, KH, B, itemsize, *, cs_itemsize=4, w_itemsize=4, bwd=False, n_parts=0):
+    """fused QK-norm + RoPE: forward reads q, k and writes q', k' -- 2 (|q| + |k|) -- plus the tables: the D/2-wide cos / sin
+    rows and the two weights, read once; pullback reads dq', dk', q, k and writes dq, dk -- 3 (|q| + |k|) -- plus the tables, dwq
+    and dwk (fp32), and the `n_parts` fp32 partial rows per tensor, written once and read once by the fold."""
+    qk = itemsize * B * L * D * (QH + KH)
+    tables = 2 * cs_itemsize * B * L * (D // 2) + 2 * w_itemsize * D
+    if not bwd:
+        return 2 * qk + tables
+    return 3 * qk + tables + 2 * 4 * D + 2 * 2 * n_parts * 4 * D

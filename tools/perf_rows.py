@@ -1,9 +1,10 @@
 """Bandwidth of the row-wise operators (online_softmax; later the norms) vs the HBM roofline.  Dev tool: one JSON line
-per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [glu [--shape=rows,n,dtype,layout ...]] [xent [--shape=rows,n,ld,dtype ...] [--crossover]] [--cpu]
+per shape.  usage: python tools/perf_rows.py [softmax] [norms] [add_norms [--shape=emb,n,dtype ...]] [glu [--shape=rows,n,dtype,layout ...]] [xent [--shape=rows,n,ld,dtype ...] [--crossover]] [qknr [--shape=B,L,QH,KH,D,dtype ...]] [--cpu]
 add_norms: the residual add fused into the norms against the two-call sequence it replaces, one JSON line per operator,
 direction and shape (profiles/add_norm/perf.jsonl is this mode's output).
 glu: the gated MLP activations against the torch sequence they replace (profiles/glu/perf.jsonl).
-xent: the cross-entropy loss against F.cross_entropy and its autograd backward (profiles/xent/perf.jsonl)."""
+xent: the cross-entropy loss against F.cross_entropy and its autograd backward (profiles/xent/perf.jsonl).
+qknr: the fused QK-norm + RoPE against the three-call sequence it replaces (profiles/qknr/perf.jsonl)."""
 import json
 import os
 import sys
@@ -345,6 +346,66 @@ def xent():
         del buf, x, dx
     if failed:
         sys.exit("fused not faster than torch: " + "; ".join(failed))
+
+
+QKNR_SHAPES = [(4, 4096, 32, 8, 128, "bf16"), (1, 32768, 32, 8, 128, "bf16"), (4, 4096, 8, 4, 256, "bf16")]
+QKNR_BAR = 0.75     # fused <= 0.75 x the sequence: midway between the byte ratio (0.5 forward, 0.6 pullback) and parity
+
+
+def qknr():
+    """Fused QK-norm + RoPE against the three calls it replaces, in the same process: forward _qk_norm_rope against _rms_norm on q,
+    _rms_norm on k and _llama_rope; pullback grad_qk_norm_rope against grad_llama_rope, grad_rms_norm on q and grad_rms_norm on k (with
+    the rms the sequence's forward saved).  Alternating, 5 repeats of timeit() each: median with the min-max spread, algorithmic TB/s
+    from workmodel.qknr_bytes, ratio of the medians, gate = ratio <= QKNR_BAR.  --out=FILE (default profiles/qknr/perf.jsonl),
+    --shape=B,L,QH,KH,D,dtype.  A missed gate ends the run with a non-zero status after every line is printed."""
+    import ctypes as C
+    qknr_bytes = pkg.workmodel.qknr_bytes
+    out = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")] or [os.path.join(ROOT, "profiles", "qknr", "perf.jsonl")])[0]
+    extra = [a.split("=", 1)[1].split(",") for a in sys.argv[1:] if a.startswith("--shape=")]
+    shapes = [(int(b), int(l), int(qh), int(kh), int(d), dt) for b, l, qh, kh, d, dt in extra] or QKNR_SHAPES
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    failed, lines = [], []
+    for B, L, QH, KH, D, dt in shapes:
+        q, dq2 = (torch.randn(B, QH, L, D, device=DEV).to(DT[dt]) for _ in range(2))
+        k, dk2 = (torch.randn(B, KH, L, D, device=DEV).to(DT[dt]) for _ in range(2))
+        wq, wk = torch.randn(D, device=DEV), torch.randn(D, device=DEV)
+        cos, sin = pkg.LlamaRotaryEmbedding(D, device=DEV)(torch.arange(L, device=DEV, dtype=torch.float32).expand(B, L))
+        isz = q.element_size()
+        _, rms_q = pkg._rms_norm(q.view(-1, D), wq)
+        _, rms_k = pkg._rms_norm(k.view(-1, D), wk)
+        n_parts = pkg._lib_ext.load().nnop_qk_norm_rope_bwd_workspace_bytes(C.byref(pkg.qknorm._desc(q, k, wq, cos, 1e-6, 0.0))) // (8 * D)
+
+        def seq_f():
+            nq, _ = pkg._rms_norm(q.view(-1, D), wq)
+            nk, _ = pkg._rms_norm(k.view(-1, D), wk)
+            return pkg._llama_rope(nq.view_as(q), nk.view_as(k), cos, sin, bwd=False)
+
+        def seq_b():
+            dnq, dnk = pkg.grad_llama_rope((dq2, dk2), cos, sin)
+            return pkg.grad_rms_norm(dnq.view(-1, D), rms_q, q.view(-1, D), wq) + pkg.grad_rms_norm(dnk.view(-1, D), rms_k, k.view(-1, D), wk)
+
+        fused_f = lambda: pkg._qk_norm_rope(q, k, wq, wk, cos, sin)
+        fused_b = lambda: pkg.grad_qk_norm_rope((dq2, dk2), q, k, wq, wk, cos, sin)
+        for op, bwd, fused, seq in (("qk_norm_rope", False, fused_f, seq_f), ("grad_qk_norm_rope", True, fused_b, seq_b)):
+            tf, ts = [], []
+            for _ in range(5):                               # alternate: fused, sequence, fused, ...
+                tf.append(timeit(fused))
+                ts.append(timeit(seq))
+            tf.sort(); ts.sort()
+            nb = qknr_bytes(D, L, QH, KH, B, isz, bwd=bwd, n_parts=n_parts if bwd else 0)
+            ratio = tf[2] / ts[2]
+            d = dict(op=op, shape=f"B{B} L{L} QH{QH} KH{KH} D{D}", dtype=dt, us=round(tf[2], 2), us_min=round(tf[0], 2), us_max=round(tf[4], 2),
+                     bytes=nb, tbps=round(nb / tf[2] / 1e6, 3), seq_us=round(ts[2], 2), seq_min=round(ts[0], 2), seq_max=round(ts[4], 2),
+                     ratio=round(ratio, 3), gate=bool(ratio <= QKNR_BAR))
+            print(json.dumps(d), flush=True)
+            lines.append(json.dumps(d))
+            if not ratio <= QKNR_BAR:
+                failed.append(f"{op} {d['shape']} {dt}: {ratio:.3f}")
+        with open(out, "w") as f:                            # rewritten after every shape: a run that is cut short keeps what it has
+            f.write("\n".join(lines) + "\n")
+        del q, k, dq2, dk2
+    if failed:
+        sys.exit(f"fused above {QKNR_BAR} x the three-call sequence: " + "; ".join(failed))
 
 
 if __name__ == "__main__":
