@@ -4,7 +4,8 @@ Holds only what the hot path needs: ``csrc/`` (hand-written gfx950 HIP kernels +
 ``include/nnop_hip.h``), the host-side mirror of the reference interface (``attention.py``; ``rope.py`` for the
 Llama rotary embedding applied to q, k right before attention -- SURVEY.md section 8(f) rank 2; ``softmax.py``, ``norms.py``,
 ``activations.py`` for the MLP's gated activation, ``losses.py`` for the cross-entropy over the LM head's logits and
-``qknorm.py`` for the fused QK-norm + RoPE of the extension library, ``include/nnop_hip_ext.h``), the
+``qknorm.py`` for the fused QK-norm + RoPE of the extension library, ``include/nnop_hip_ext.h``, ``moe.py`` for the
+mixture-of-experts gate and dispatch plan of the third library, ``include/nnop_hip_moe.h``), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -21,7 +22,9 @@ from .norms import (add_rms_norm, _add_rms_norm, grad_add_rms_norm, add_layer_no
 from .activations import (glu, swiglu, geglu, glu_packed, _glu, grad_glu, grad_glu_packed, glu_into, grad_glu_into)
 from .losses import cross_entropy, _cross_entropy, grad_cross_entropy
 from .qknorm import qk_norm_rope, _qk_norm_rope, grad_qk_norm_rope, qk_norm_rope_into, grad_qk_norm_rope_into
-from . import _lib, _lib_ext, activations, losses, qknorm, shard, workmodel
+from .moe import (moe_router, _moe_router, grad_moe_router, moe_router_into, grad_moe_router_into, moe_dispatch_plan,
+                  moe_dispatch_plan_into)
+from . import _lib, _lib_ext, _lib_moe, activations, losses, moe, qknorm, shard, workmodel
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -31,5 +34,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "glu", "swiglu", "geglu", "glu_packed", "_glu", "grad_glu", "grad_glu_packed", "glu_into", "grad_glu_into", "activations",
            "cross_entropy", "_cross_entropy", "grad_cross_entropy", "losses",
            "qk_norm_rope", "_qk_norm_rope", "grad_qk_norm_rope", "qk_norm_rope_into", "grad_qk_norm_rope_into", "qknorm",
-           "shard", "workmodel", "_lib", "_lib_ext"]
+           "moe_router", "_moe_router", "grad_moe_router", "moe_router_into", "grad_moe_router_into", "moe_dispatch_plan",
+           "moe_dispatch_plan_into", "moe",
+           "shard", "workmodel", "_lib", "_lib_ext", "_lib_moe"]
 __version__ = "0.1.0"
