@@ -13,7 +13,7 @@
 // Arithmetic in fp32, one rounding on store.  No LDS, no atomics, no workspace.
 // Bound: HBM.
 #include <limits.h>
-#include "fa_common.hpp"
+#include "row_common.hpp"
 #include "fa_launch.hpp"
 
 // Every path, layout and direction must give bitwise the same a(g) and a'(g): nothing below may be contracted into an
@@ -123,19 +123,11 @@ template <int ACT> NNOP_DEV void glu_bwd_elem(float dy, float g, float u, float 
     du = (dy * a) * um;
 }
 
-// The one rounding on store, of an fp32 value that EXISTS: without the fence the compiler folds the last fp32 multiply and the
-// conversion to fp16 into one v_fma_mixlo_f16 (a single rounding of the exact product) on the element-wise path, while the
-// 16-byte path multiplies in fp32 and converts pairs (v_cvt_pk_f16_f32) -- two roundings, and about one result in 2^13
-// differs between the paths.  The fence (fa_common.hpp `landed`: an empty statement, no instruction) keeps the product in fp32.
-template <typename T> NNOP_DEV T glu_round(float x) {
-    landed(x);
-    return from_f32<T>(x);
-}
-
 // ---- the kernel -------------------------------------------------------------------------------------------------------
 // VEC: elements per 16-byte chunk on the vector path (8 x 16-bit, 4 x fp32), 1 on the element-wise path (n or ld no
 // multiple of that, or a base that is not 16-byte aligned).  IL: interleaved layout.  U: chunks in flight per lane; the
 // U chunks of a lane are 256 chunks apart, so each of the U load instructions of a wave is contiguous.
+// Every result is stored through round_store (row_common.hpp): the vector and the element path round alike.
 // The pointers carry no __restrict__: an output may be the input it replaces (include/nnop_hip.h); a lane reads its
 // chunk before it writes it, and no lane touches another lane's chunk.
 template <typename T, int ACT, bool IL, bool BWD, int VEC, int U>
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(256) void glu_kernel(const GluParams p) {
             tv y;
 #pragma unroll
             for (int j = 0; j < VEC; ++j)
-                y[j] = glu_round<T>(glu_fwd_elem<ACT>(to_f32(gv[k][j]), to_f32(uv[k][j]), p.alpha, p.limit));
+                y[j] = round_store<T>(glu_fwd_elem<ACT>(to_f32(gv[k][j]), to_f32(uv[k][j]), p.alpha, p.limit));
             *reinterpret_cast<tv*>((T*)p.o0 + io[k]) = y;
         } else {
             tv dg, du;
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(256) void glu_kernel(const GluParams p) {
             for (int j = 0; j < VEC; ++j) {
                 float a, b;
                 glu_bwd_elem<ACT>(to_f32(dv[k][j]), to_f32(gv[k][j]), to_f32(uv[k][j]), p.alpha, p.limit, a, b);
-                dg[j] = glu_round<T>(a); du[j] = glu_round<T>(b);
+                dg[j] = round_store<T>(a); du[j] = round_store<T>(b);
             }
             if constexpr (IL) {
                 tv lo, hi;
@@ -215,10 +207,7 @@ static int launch_glu_t(GluParams p, long long rows, hipStream_t s) {
     // the vector path issues 16-byte accesses at multiples of V elements from every base: all bases 16-byte aligned, n and
     // ld multiples of V (the halves of a packed projection, up = gate + n, pass exactly when n is).  Everything else --
     // odd n, an offset view, a misaligned half -- takes the element-wise instantiation.
-    const uintptr_t bases = reinterpret_cast<uintptr_t>(p.o0) | reinterpret_cast<uintptr_t>(p.o1) |
-                            reinterpret_cast<uintptr_t>(p.dy) | reinterpret_cast<uintptr_t>(p.g) |
-                            reinterpret_cast<uintptr_t>(p.u);
-    const bool vec = (bases & 15) == 0 && p.n % V == 0 && p.ld % V == 0;
+    const bool vec = aligned16({p.o0, p.o1, p.dy, p.g, p.u}) && p.n % V == 0 && p.ld % V == 0;
     if (p.ld > (LLONG_MAX >> 4) / rows) return NNOP_ERR_SHAPE;                     // rows * ld in bytes fits 64 bits
     p.cpr = vec ? p.n / V : p.n;
     p.n_items = rows * p.cpr;
@@ -248,12 +237,7 @@ template <bool BWD> static int launch_glu_any(const nnop_glu_desc& d, GluParams 
     p.n = d.n; p.ld = d.ld;
     p.alpha = d.alpha; p.limit = d.limit;
     p.cpr = p.n_items = 0; p.small = 0;                          // set per instantiation in launch_glu_t
-    switch (d.dtype) {
-        case NNOP_F32:  return launch_glu_act<float, BWD>(d, p, s);
-        case NNOP_F16:  return launch_glu_act<_Float16, BWD>(d, p, s);
-        case NNOP_BF16: return launch_glu_act<__bf16, BWD>(d, p, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d.dtype, [&](auto t) { return launch_glu_act<typename decltype(t)::type, BWD>(d, p, s); });
 }
 
 int launch_glu(const nnop_glu_desc& d, void* y, const void* gate, const void* up, hipStream_t s) {

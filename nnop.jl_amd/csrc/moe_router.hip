@@ -14,7 +14,6 @@
 // Bound: launch latency and the k dependent reduction rounds; the logits of 8192 tokens x 128 experts are 2 MB.
 //
 // No lane leaves the forward kernel in front of a cross-lane exchange: a group past the last row works on the last row and stores nothing.
-#include <initializer_list>
 #include "row_common.hpp"
 #include "moe.hpp"
 
@@ -62,12 +61,6 @@ template <int G> NNOP_DEV double moe_group_sum(double v) {
     v += xlane_d<1>(v); v += xlane_d<2>(v); v += xlane_d<4>(v); v += xlane_d<8>(v);
     if constexpr (G > 16) v += xlane_d<16>(v);
     if constexpr (G > 32) v += xlane_d<32>(v);
-    return v;
-}
-template <int G> NNOP_DEV float moe_group_sum(float v) {
-    v += xlane<1>(v); v += xlane<2>(v); v += xlane<4>(v); v += xlane<8>(v);
-    if constexpr (G > 16) v += xlane<16>(v);
-    if constexpr (G > 32) v += xlane<32>(v);
     return v;
 }
 
@@ -203,12 +196,6 @@ __global__ __launch_bounds__(256) void moe_router_bwd_kernel(const MoeRouterPara
     }
 }
 
-static inline bool aligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t u = 0;
-    for (const void* q : ptrs) u |= reinterpret_cast<uintptr_t>(q);
-    return (u & 15) == 0;
-}
-
 template <typename T, int VEC, int LPR, int NE> static void launch_shape(const MoeRouterParams& p, bool bwd, hipStream_t s) {
     const long long items = (long long)p.T * LPR;
     const dim3 grid((unsigned)((items + 255) / 256)), block(256);
@@ -241,12 +228,7 @@ template <typename T> static int launch_moe_router_t(const MoeRouterParams& p, b
 
 static int launch_moe_router(const nnop_moe_router_desc& d, MoeRouterParams p, bool bwd, hipStream_t s) {
     p.T = d.tokens; p.E = d.experts; p.K = d.topk; p.norm = d.norm; p.ld = d.ld;
-    switch (d.dtype) {
-        case NNOP_F32: return launch_moe_router_t<float>(p, bwd, s);
-        case NNOP_F16: return launch_moe_router_t<_Float16>(p, bwd, s);
-        case NNOP_BF16: return launch_moe_router_t<__bf16>(p, bwd, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d.dtype, [&](auto t) { return launch_moe_router_t<typename decltype(t)::type>(p, bwd, s); });
 }
 
 int launch_moe_router_fwd(const nnop_moe_router_desc& d, int32_t* idx, float* w, float* lse, const void* logits, hipStream_t s) {

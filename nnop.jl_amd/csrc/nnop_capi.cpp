@@ -5,6 +5,7 @@
 // become status codes; allocation of outputs and scratch moves to the caller; the launch is
 // asynchronous on the caller's stream (src/attention.jl:170-176 never synchronises either).
 #include "fa_launch.hpp"
+#include "host_common.hpp"
 #include "nnop_debug.h"
 #include "tuning.hpp"
 #include <limits.h>
@@ -38,7 +39,7 @@ int tune_get(int key) {
 
 static int check_desc(const nnop_fa_desc* d) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->emb <= 0 || d->ql <= 0 || d->kl <= 0 || d->qh <= 0 || d->kh <= 0 || d->batch <= 0) return NNOP_ERR_SHAPE;
     const int emb_k = d->emb_k ? d->emb_k : d->emb;
     const int emb_v = d->emb_v ? d->emb_v : emb_k;
@@ -56,11 +57,10 @@ static int check_desc(const nnop_fa_desc* d) {
 }
 // Base alignment (NNOP_ERR_ALIGN): the MFMA kernels move q, k, v, o, the gradients, the bias and the workspace with 16-byte vector
 // accesses and LDS-DMA from the raw base; the plain-HIP kernels (embedding dims outside the tiled set) access single elements.
-static inline bool misaligned(const void* p, size_t a) { return p && ((uintptr_t)p & (a - 1)) != 0; }
-static inline size_t elem_bytes(const nnop_fa_desc* d) { return d->dtype == NNOP_F32 ? 4 : 2; }
+// The optional arguments (pair, dpair, sinks, dsinks) go through `misaligned` as they are: NULL counts as aligned.
 static inline size_t tensor_align(const nnop_fa_desc* d) {
     const bool tiled = emb_tiled(d->emb) || d->emb == 256;
-    return tiled ? 16 : elem_bytes(d);
+    return tiled ? 16 : dtype_bytes(d->dtype);
 }
 // per-call options (checked after check_desc, whose order is the reference's)
 static int check_opts(const nnop_fa_opts* o) {
@@ -71,7 +71,7 @@ static int check_opts(const nnop_fa_opts* o) {
     return NNOP_OK;
 }
 // logit soft-capping (checked after the options): 0 = none, else finite and positive
-static int check_softcap(float c) { return (c >= 0.f && c <= 3.4028234664e38f) ? NNOP_OK : NNOP_ERR_OPTS; }     // (false for NaN)
+static int check_softcap(float c) { return finite_nonneg(c) ? NNOP_OK : NNOP_ERR_OPTS; }
 // pair / dpair [B][KL][QL][QH]: inside one kv tile the kernels address the bias with 32-bit element offsets
 // (local key < 64) * QL * QH
 static int check_pair(const nnop_fa_desc* d) {
@@ -232,25 +232,20 @@ int nnop_fa_fwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const f
     if (!o || !ms || !ls || !q || !k || !v) return NNOP_ERR_NULL;
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
     {
-        const size_t ta = tensor_align(d), ea = elem_bytes(d);
+        const size_t ta = tensor_align(d), ea = dtype_bytes(d->dtype);
         if (misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(sinks, sizeof(float)))
             return NNOP_ERR_ALIGN;
     }
     FwdArgs a{o, ms, ls, q, k, v, pair, kpad_mask, fa_window(*d, opts), sinks, softcap};
     hipStream_t s = (hipStream_t)stream;
-    switch (d->dtype) {
-        case NNOP_F32:  return launch_fwd<float>(*d, a, s);
-        case NNOP_F16:  return launch_fwd<_Float16>(*d, a, s);
-        case NNOP_BF16: return launch_fwd<__bf16>(*d, a, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d->dtype, [&](auto t) { return launch_fwd<typename decltype(t)::type>(*d, a, s); });
 }
 
 int nnop_llama_rope(const nnop_rope_desc* d, void* q_out, void* k_out, const void* q, const void* k,
                     const void* cos, const void* sin, float sin_sign, nnop_stream_t stream) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->cs_dtype != NNOP_F32 && d->cs_dtype != d->dtype) return NNOP_ERR_DTYPE;
     if (d->dim <= 0 || (d->dim & 1) || d->seq <= 0 || d->qh <= 0 || d->kh <= 0 || d->batch <= 0) return NNOP_ERR_SHAPE;
     if (!q_out || !k_out || !q || !k || !cos || !sin) return NNOP_ERR_NULL;
@@ -259,7 +254,7 @@ int nnop_llama_rope(const nnop_rope_desc* d, void* q_out, void* k_out, const voi
 
 static int check_softmax(const nnop_softmax_desc* d) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->n <= 0 || d->batch <= 0) return NNOP_ERR_SHAPE;
     return NNOP_OK;
 }
@@ -281,7 +276,7 @@ int nnop_online_softmax_bwd(const nnop_softmax_desc* d, void* dx, const void* dy
 
 static int check_norm(const nnop_norm_desc* d) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->w_dtype != NNOP_F32 && d->w_dtype != d->dtype) return NNOP_ERR_DTYPE;
     if (d->emb <= 0 || d->n <= 0 || d->n > 0x7fffffffLL || d->reserved != 0) return NNOP_ERR_SHAPE;
     return NNOP_OK;
@@ -360,88 +355,65 @@ int nnop_add_layer_norm_bwd(const nnop_norm_desc* d, void* dx, void* dw, void* d
 
 // descriptor, then pointers, then alignment; `ptrs`: the arguments that must be non-NULL, `absent`: those that the interleaved
 // layout forbids (up, dup)
-static int check_glu(const nnop_glu_desc* d, const void* const* ptrs, int n_ptrs, const void* const* absent, int n_absent) {
+static int check_glu(const nnop_glu_desc* d, std::initializer_list<const void*> ptrs, std::initializer_list<const void*> absent) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->act < NNOP_GLU_SILU || d->act > NNOP_GLU_SWIGLU_OAI) return NNOP_ERR_OPTS;
     if (d->layout != NNOP_GLU_SPLIT && d->layout != NNOP_GLU_INTERLEAVED) return NNOP_ERR_OPTS;
-    if (d->act == NNOP_GLU_SWIGLU_OAI) {                                                       // (the comparisons are false for NaN)
-        if (!(d->alpha >= -3.4028234664e38f && d->alpha <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
-        if (!(d->limit > 0.f && d->limit <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
-    }
+    if (d->act == NNOP_GLU_SWIGLU_OAI && !(finite(d->alpha) && finite(d->limit) && d->limit > 0.f)) return NNOP_ERR_OPTS;
     if (d->rows <= 0 || d->n <= 0 || d->reserved != 0) return NNOP_ERR_SHAPE;
     const bool il = d->layout == NNOP_GLU_INTERLEAVED;
     if (il ? (d->n > LLONG_MAX / 2 || d->ld != 2 * d->n) : d->ld < d->n) return NNOP_ERR_SHAPE;
-    for (int i = 0; i < n_ptrs; ++i)
-        if (!ptrs[i]) return NNOP_ERR_NULL;
-    for (int i = 0; i < n_absent; ++i)
-        if (il ? absent[i] != nullptr : absent[i] == nullptr) return NNOP_ERR_NULL;
-    const size_t ea = d->dtype == NNOP_F32 ? 4 : 2;
-    for (int i = 0; i < n_ptrs; ++i)
-        if (misaligned(ptrs[i], ea)) return NNOP_ERR_ALIGN;
-    for (int i = 0; i < n_absent; ++i)
-        if (misaligned(absent[i], ea)) return NNOP_ERR_ALIGN;
+    const size_t ea = dtype_bytes(d->dtype);
+    const int st = check_ptrs({{ptrs, ea}}, [&] {
+        for (const void* q : absent)
+            if (il ? q != nullptr : q == nullptr) return NNOP_ERR_NULL;
+        return NNOP_OK;
+    });
+    if (st != NNOP_OK) return st;
+    for (const void* q : absent)
+        if (misaligned(q, ea)) return NNOP_ERR_ALIGN;
     return NNOP_OK;
 }
 
 int nnop_glu(const nnop_glu_desc* d, void* y, const void* gate, const void* up, nnop_stream_t stream) {
-    const void* const ptrs[] = {y, gate};
-    const void* const absent[] = {up};
-    const int st = check_glu(d, ptrs, 2, absent, 1);
+    const int st = check_glu(d, {y, gate}, {up});
     if (st != NNOP_OK) return st;
     return launch_glu(*d, y, gate, up, (hipStream_t)stream);
 }
 
 int nnop_glu_bwd(const nnop_glu_desc* d, void* dgate, void* dup, const void* dy, const void* gate, const void* up,
                  nnop_stream_t stream) {
-    const void* const ptrs[] = {dgate, dy, gate};
-    const void* const absent[] = {dup, up};
-    const int st = check_glu(d, ptrs, 3, absent, 2);
+    const int st = check_glu(d, {dgate, dy, gate}, {dup, up});
     if (st != NNOP_OK) return st;
     return launch_glu_bwd(*d, dgate, dup, dy, gate, up, (hipStream_t)stream);
 }
 
 // descriptor (dtype, options, shape), then pointers, then alignment; `elems`: logits / dlogits (element size), `f32s`: loss, lse, dloss
-static int check_xent(const nnop_xent_desc* d, bool bwd, const void* const* elems, int n_elems, const void* const* f32s, int n_f32s,
-                      const void* targets) {
+static int check_xent(const nnop_xent_desc* d, bool bwd, std::initializer_list<const void*> elems,
+                      std::initializer_list<const void*> f32s, const void* targets) {
     if (!d) return NNOP_ERR_NULL;
-    if (d->dtype != NNOP_F32 && d->dtype != NNOP_F16 && d->dtype != NNOP_BF16) return NNOP_ERR_DTYPE;
+    if (!known_dtype(d->dtype)) return NNOP_ERR_DTYPE;
     if (d->index_bytes != 4 && d->index_bytes != 8) return NNOP_ERR_OPTS;
     if (d->index_base != 0 && d->index_base != 1) return NNOP_ERR_OPTS;
     if (d->reserved != 0 || !(d->reserved_f == 0.f)) return NNOP_ERR_OPTS;
     if (!(d->label_smoothing >= 0.f && d->label_smoothing <= 1.f)) return NNOP_ERR_OPTS;      // (the comparisons are false for NaN)
-    if (!(d->z_loss >= 0.f && d->z_loss <= 3.4028234664e38f)) return NNOP_ERR_OPTS;
-    if (check_softcap(d->softcap) != NNOP_OK) return NNOP_ERR_OPTS;
+    if (!finite_nonneg(d->z_loss) || !finite_nonneg(d->softcap)) return NNOP_ERR_OPTS;
     if (d->rows <= 0 || d->n <= 0 || d->ld < d->n || (bwd && d->ld_grad < d->n)) return NNOP_ERR_SHAPE;
     if (d->n > 0x7fffffffLL || d->rows > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    for (int i = 0; i < n_elems; ++i)
-        if (!elems[i]) return NNOP_ERR_NULL;
-    for (int i = 0; i < n_f32s; ++i)
-        if (!f32s[i]) return NNOP_ERR_NULL;
-    if (!targets) return NNOP_ERR_NULL;
-    const size_t ea = d->dtype == NNOP_F32 ? 4 : 2;
-    for (int i = 0; i < n_elems; ++i)
-        if (misaligned(elems[i], ea)) return NNOP_ERR_ALIGN;
-    for (int i = 0; i < n_f32s; ++i)
-        if (misaligned(f32s[i], sizeof(float))) return NNOP_ERR_ALIGN;
-    if (misaligned(targets, (size_t)d->index_bytes)) return NNOP_ERR_ALIGN;
-    return NNOP_OK;
+    return check_ptrs({{elems, dtype_bytes(d->dtype)}, {f32s, sizeof(float)}, {{targets}, (size_t)d->index_bytes}});
 }
 
 int nnop_cross_entropy(const nnop_xent_desc* d, float* loss, float* lse, const void* logits, const void* targets,
                        nnop_stream_t stream) {
-    const void* const elems[] = {logits};
-    const void* const f32s[] = {loss, lse};
-    const int st = check_xent(d, false, elems, 1, f32s, 2, targets);
+    const int st = check_xent(d, false, {logits}, {loss, lse}, targets);
     if (st != NNOP_OK) return st;
     return launch_xent(*d, loss, lse, logits, targets, (hipStream_t)stream);
 }
 
 int nnop_cross_entropy_bwd(const nnop_xent_desc* d, void* dlogits, const float* dloss, const float* lse, const void* logits,
                            const void* targets, nnop_stream_t stream) {
-    const void* const elems[] = {dlogits, logits};
-    const void* const f32s[] = {dloss, lse};
-    const int st = check_xent(d, true, elems, 2, f32s, 2, targets);
+    const int st = check_xent(d, true, {dlogits, logits}, {dloss, lse}, targets);
     if (st != NNOP_OK) return st;
     return launch_xent_bwd(*d, dlogits, dloss, lse, logits, targets, (hipStream_t)stream);
 }
@@ -498,7 +470,7 @@ int nnop_fa_bwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const f
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
     if (workspace_bytes < bwd_workspace_bytes(*d)) return NNOP_ERR_WORKSPACE;
     {
-        const size_t ta = tensor_align(d), ea = elem_bytes(d);
+        const size_t ta = tensor_align(d), ea = dtype_bytes(d->dtype);
         if (misaligned(dq, ta) || misaligned(dk, ta) || misaligned(dv, ta) || misaligned(dpair, ta) || misaligned(d_o, ta) ||
             misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(workspace, 16) || misaligned(sinks, sizeof(float)) ||
@@ -509,18 +481,11 @@ int nnop_fa_bwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const f
               sinks, dsinks, softcap};
     hipStream_t s = (hipStream_t)stream;
     // dQ, dK, dV (and dpair) need nothing for a sink: they recompute P from (ms, ls), which include it.  dsinks: one more pass behind them
-    switch (d->dtype) {
-        case NNOP_F32:
-            st = launch_bwd<float>(*d, a, s);
-            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<float>(*d, a, s) : st;
-        case NNOP_F16:
-            st = launch_bwd<_Float16>(*d, a, s);
-            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<_Float16>(*d, a, s) : st;
-        case NNOP_BF16:
-            st = launch_bwd<__bf16>(*d, a, s);
-            return (st == NNOP_OK && sinks) ? launch_bwd_sinks<__bf16>(*d, a, s) : st;
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d->dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const int st = launch_bwd<T>(*d, a, s);
+        return (st == NNOP_OK && sinks) ? launch_bwd_sinks<T>(*d, a, s) : st;
+    });
 }
 
 }  // extern "C"

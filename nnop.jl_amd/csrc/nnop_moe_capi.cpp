@@ -3,15 +3,11 @@
 // Every argument check happens here, in the header's order, before anything touches the device.  The library exports these five
 // functions and nothing else (nnop_moe.map); it links nothing from libnnop_hip.so or libnnop_hip_ext.so.
 #include "moe.hpp"
-#include <stdint.h>
+#include "host_common.hpp"
 
 #define NNOP_MOE_API extern "C" __attribute__((visibility("default")))
 
 namespace nnop {
-
-static inline bool known_dtype(int32_t t) { return t == NNOP_F32 || t == NNOP_F16 || t == NNOP_BF16; }
-static inline size_t dtype_bytes(int32_t t) { return t == NNOP_F32 ? 4 : 2; }
-static inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 // dtype, then options, then shape (the descriptor must not be NULL)
 static int check_router_desc(const nnop_moe_router_desc* d) {
@@ -33,19 +29,6 @@ static int check_plan_desc(const nnop_moe_plan_desc* d) {
     return NNOP_OK;
 }
 
-// NULL, then alignment: `elems` are of dtype, `words` fp32 or int32
-static int check_ptrs(int32_t dtype, const void* const* elems, int n_elems, const void* const* words, int n_words) {
-    for (int i = 0; i < n_elems; ++i)
-        if (!elems[i]) return NNOP_ERR_NULL;
-    for (int i = 0; i < n_words; ++i)
-        if (!words[i]) return NNOP_ERR_NULL;
-    for (int i = 0; i < n_elems; ++i)
-        if (misaligned(elems[i], dtype_bytes(dtype))) return NNOP_ERR_ALIGN;
-    for (int i = 0; i < n_words; ++i)
-        if (misaligned(words[i], 4)) return NNOP_ERR_ALIGN;
-    return NNOP_OK;
-}
-
 }  // namespace nnop
 
 using namespace nnop;
@@ -57,9 +40,7 @@ NNOP_MOE_API int nnop_moe_router(const nnop_moe_router_desc* d, int32_t* idx, fl
     if (!d) return NNOP_ERR_NULL;
     int st = check_router_desc(d);
     if (st != NNOP_OK) return st;
-    const void* const elems[] = {logits};
-    const void* const words[] = {idx, w, lse};
-    st = check_ptrs(d->dtype, elems, 1, words, 3);
+    st = check_ptrs({{{logits}, dtype_bytes(d->dtype)}, {{idx, w, lse}, 4}});
     if (st != NNOP_OK) return st;
     return launch_moe_router_fwd(*d, idx, w, lse, logits, (hipStream_t)stream);
 }
@@ -69,11 +50,9 @@ NNOP_MOE_API int nnop_moe_router_bwd(const nnop_moe_router_desc* d, void* dlogit
     if (!d) return NNOP_ERR_NULL;
     int st = check_router_desc(d);
     if (st != NNOP_OK) return st;
-    const void* const elems[] = {dlogits, logits};
-    const void* const words[] = {dw, w, idx, lse};
-    st = check_ptrs(d->dtype, elems, 2, words, 4);
+    st = check_ptrs({{{dlogits, logits}, dtype_bytes(d->dtype)}, {{dw, w, idx, lse}, 4}});
     if (st != NNOP_OK) return st;
-    if (dlse && misaligned(dlse, 4)) return NNOP_ERR_ALIGN;         // optional: NULL counts as 0
+    if (misaligned(dlse, 4)) return NNOP_ERR_ALIGN;                 // optional: NULL counts as 0, and as aligned
     return launch_moe_router_bwd(*d, dlogits, dw, dlse, w, idx, lse, logits, (hipStream_t)stream);
 }
 
@@ -87,13 +66,8 @@ NNOP_MOE_API int nnop_moe_plan(const nnop_moe_plan_desc* d, int32_t* counts, int
     if (!d) return NNOP_ERR_NULL;
     int st = check_plan_desc(d);
     if (st != NNOP_OK) return st;
-    const void* const words[] = {counts, offsets, perm, slot, idx};
-    for (const void* q : words)
-        if (!q) return NNOP_ERR_NULL;
-    if (!workspace) return NNOP_ERR_NULL;
-    for (const void* q : words)
-        if (misaligned(q, 4)) return NNOP_ERR_ALIGN;
-    if (misaligned(workspace, 16)) return NNOP_ERR_ALIGN;
+    st = check_ptrs({{{counts, offsets, perm, slot, idx}, 4}, {{workspace}, 16}});
+    if (st != NNOP_OK) return st;
     if (workspace_bytes < moe_plan_ws_bytes(*d)) return NNOP_ERR_WORKSPACE;
     return launch_moe_plan(*d, counts, offsets, perm, slot, idx, workspace, (hipStream_t)stream);
 }

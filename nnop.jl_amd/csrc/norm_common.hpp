@@ -12,7 +12,7 @@
 // element-strided accesses).  Pullback: the reference gives a workgroup 4 rows and keeps dw/db in LDS with a barrier per
 // element step (:101-103), then sums n/4 partial rows with a separate `sum`; here a group of lanes walks rows g, g+P, ..
 // and every lane owns fixed columns, so dw/db accumulate in REGISTERS; the <= 1024 partial rows are folded by one small
-// second kernel in a fixed order (deterministic, no atomics).
+// second kernel (row_common.hpp fold_partial_rows_kernel) in a fixed order (deterministic, no atomics).
 // Bound: HBM -- forward 2*emb*sizeof(T) per row; pullback 3*emb*sizeof(T) per row (+ the partials, <= 8 %).
 // With the residual add fused in (ADD = true, below): 4*emb*sizeof(T) per row in both directions, against 5 and 6 as two calls.
 #pragma once
@@ -397,38 +397,6 @@ __global__ __launch_bounds__(256) void norm_bwd_generic_kernel(const NormParams 
     }
 }
 
-// dw[e] (blockIdx.y = 0) / db[e] (blockIdx.y = 1) = sum over the partial rows in a fixed order: a workgroup takes 32
-// columns x 32 slices of rows (four independent accumulators per lane keep loads in flight), slices meet through LDS
-template <typename O>
-__global__ __launch_bounds__(1024) void norm_fold_kernel(O* __restrict__ out_w, O* __restrict__ out_b,
-                                                          const float* __restrict__ part_w,
-                                                          const float* __restrict__ part_b, int n_parts, int emb) {
-    __shared__ float sm[32][33];
-    const float* __restrict__ part = blockIdx.y ? part_b : part_w;
-    O* __restrict__ out = blockIdx.y ? out_b : out_w;
-    const int c = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + c;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (col < emb) {
-        int g = sl;
-        for (; g + 96 < n_parts; g += 128) {
-            s0 += part[(size_t)g * emb + col];
-            s1 += part[(size_t)(g + 32) * emb + col];
-            s2 += part[(size_t)(g + 64) * emb + col];
-            s3 += part[(size_t)(g + 96) * emb + col];
-        }
-        for (; g < n_parts; g += 32) s0 += part[(size_t)g * emb + col];
-    }
-    sm[sl][c] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (sl == 0 && col < emb) {
-        float t = sm[0][c];
-#pragma unroll
-        for (int k = 1; k < 32; ++k) t += sm[k][c];
-        out[col] = from_f32<O>(t);
-    }
-}
-
 // Number of partial rows (= persistent pullback workgroups) for n rows of emb columns.  Measured on MI355X
 // (tools/norm_cap.sh): more workgroups hide the per-row reduce latency, but every partial row is emb*4 bytes written
 // and read again by the fold -- best is ~2 Mi partial elements: 256 rows at emb >= 8192, 512 at 4096, 1024 below 2048.
@@ -452,11 +420,9 @@ static inline size_t norm_bwd_ws_bytes(const nnop_norm_desc& d, bool ln) {
     return (size_t)norm_bwd_max_parts(d.n) * (size_t)d.emb * sizeof(float) * (ln ? 2 : 1);
 }
 
-template <typename T, typename W, bool LN, bool ADD = false> static int launch_norm_fwd_t(NormParams p, hipStream_t s) {
-    const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.w | (uintptr_t)p.b | (uintptr_t)p.r |
-                           (uintptr_t)p.h) & 15) == 0;
+template <typename T, typename W, bool LN, bool ADD> static int launch_norm_fwd_t(NormParams p, hipStream_t s) {
     bool done = false;
-    if (aligned)
+    if (aligned16({p.out, p.a, p.w, p.b, p.r, p.h}))
         done = dispatch_row_shape<T, 1>(p.emb, [&](auto shape) {
             constexpr int G = decltype(shape)::G, C = decltype(shape)::C;
             constexpr int RPB = G >= 256 ? 1 : 256 / G, NT = G > 256 ? G : 256;
@@ -467,14 +433,13 @@ template <typename T, typename W, bool LN, bool ADD = false> static int launch_n
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
-// O: element type of dw / db (fp32 for RMSNorm, W for LayerNorm).  ADD: p.r = dh, not NULL (a call without dh is the plain one)
-template <typename T, typename W, typename O, bool LN, bool ADD = false>
+// dw / db are of type fp32 for RMSNorm, W for LayerNorm.  ADD: p.r = dh, not NULL (a call without dh is the plain one)
+template <typename T, typename W, bool LN, bool ADD>
 static int launch_norm_bwd_t(NormParams p, void* dw, void* db, hipStream_t s) {
-    const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.x | (uintptr_t)p.w | (uintptr_t)p.part_w |
-                           (uintptr_t)p.part_b | (uintptr_t)p.r) & 15) == 0;
+    typedef std::conditional_t<LN, W, float> O;
     int parts = 0;
     bool done = false;
-    if (aligned)
+    if (aligned16({p.out, p.a, p.x, p.w, p.part_w, p.part_b, p.r}))
         done = dispatch_row_shape_narrow<T>(p.emb, [&](auto shape) {
             constexpr int G = decltype(shape)::G, C = decltype(shape)::C;
             constexpr int RPB = G >= 256 ? 1 : 256 / G, NT = G > 256 ? G : 256;
@@ -487,9 +452,28 @@ static int launch_norm_bwd_t(NormParams p, void* dw, void* db, hipStream_t s) {
         hipLaunchKernelGGL((norm_bwd_generic_kernel<T, W, LN, ADD>), dim3(parts), dim3(256), 0, s, p);
     }
     const unsigned fg = (unsigned)((p.emb + 31) / 32);
-    hipLaunchKernelGGL((norm_fold_kernel<O>), dim3(fg, LN ? 2 : 1), dim3(1024), 0, s, (O*)dw, (O*)db,
+    hipLaunchKernelGGL((fold_partial_rows_kernel<O>), dim3(fg, LN ? 2 : 1), dim3(1024), 0, s, (O*)dw, (O*)db,
                        (const float*)p.part_w, (const float*)p.part_b, parts, p.emb);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
+}
+
+// ---- what the eight launchers of rms_norm.hip / layer_norm.hip share: the descriptor's part of the parameters, the dtype dispatch ----
+static inline NormParams norm_params(const nnop_norm_desc& d) {
+    NormParams p{};
+    p.emb = d.emb; p.n = d.n; p.inv_emb = 1.0f / (float)d.emb;     // rms_norm.jl:127, layer_norm.jl:160
+    return p;
+}
+// T of d.dtype; W = float for fp32 weights, else T
+template <bool LN, bool ADD> static int launch_norm_fwd(const nnop_norm_desc& d, const NormParams& p, hipStream_t s) {
+    return dispatch_dtype_side(d.dtype, d.w_dtype, [&](auto t, auto w) {
+        return launch_norm_fwd_t<typename decltype(t)::type, typename decltype(w)::type, LN, ADD>(p, s);
+    });
+}
+template <bool LN, bool ADD>
+static int launch_norm_bwd(const nnop_norm_desc& d, const NormParams& p, void* dw, void* db, hipStream_t s) {
+    return dispatch_dtype_side(d.dtype, d.w_dtype, [&](auto t, auto w) {
+        return launch_norm_bwd_t<typename decltype(t)::type, typename decltype(w)::type, LN, ADD>(p, dw, db, s);
+    });
 }
 
 }  // namespace nnop

@@ -8,11 +8,11 @@
 // (position, batch)) come through L2.  fp32 arithmetic, one rounding on store; nothing is saved for the pullback, which reads x
 // anyway and recomputes rstd.
 // Pullback: persistent workgroups, a group of lanes walks rows g, g + n_groups, .. of q, then of k, every lane owning fixed columns,
-// so dwq / dwk accumulate in registers; one partial row per workgroup and tensor, folded by a second kernel in a fixed order.
+// so dwq / dwk accumulate in registers; one partial row per workgroup and tensor, folded by a second kernel
+// (row_common.hpp fold_partial_rows_kernel) in a fixed order.
 // Bound: HBM -- forward 2 (|q| + |k|), pullback 3 (|q| + |k|) (+ the tables, + the partials).
 //
 // No lane leaves a kernel in front of a cross-lane exchange: a group past the last row works on a clamped row and skips its stores.
-#include <initializer_list>
 #include "row_common.hpp"
 #include "qk_norm_rope.hpp"
 
@@ -77,17 +77,6 @@ template <typename E, bool VEC> struct HalfRegs {
         }
     }
 };
-
-// sum over an aligned group of G = 2^k lanes of a wave, result in every lane of the group
-template <int G> NNOP_DEV float group_sum(float v) {
-    if constexpr (G > 1) v += xlane<1>(v);
-    if constexpr (G > 2) v += xlane<2>(v);
-    if constexpr (G > 4) v += xlane<4>(v);
-    if constexpr (G > 8) v += xlane<8>(v);
-    if constexpr (G > 16) v += xlane<16>(v);
-    if constexpr (G > 32) v += xlane<32>(v);
-    return v;
-}
 
 // where a head row of one tensor lives: r = (b * H + h) * L + l is its row index in memory as well
 struct QknrRow { size_t x, cs; };
@@ -223,36 +212,6 @@ __global__ __launch_bounds__(256) void qknr_bwd_kernel(const QknrParams p) {
     }
 }
 
-// dwq (blockIdx.y = 0) / dwk (1): the n_parts partial rows of a tensor summed in a fixed order -- a workgroup takes 32 columns x 32
-// slices of rows, slices meet through LDS (the shape of norm_fold_kernel, norm_common.hpp)
-__global__ __launch_bounds__(1024) void qknr_fold_kernel(float* __restrict__ dwq, float* __restrict__ dwk,
-                                                          const float* __restrict__ part_all, int n_parts, int D) {
-    __shared__ float sm[32][33];
-    const float* __restrict__ part = part_all + (size_t)blockIdx.y * n_parts * D;
-    float* __restrict__ out = blockIdx.y ? dwk : dwq;
-    const int c = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + c;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (col < D) {
-        int g = sl;
-        for (; g + 96 < n_parts; g += 128) {
-            s0 += part[(size_t)g * D + col];
-            s1 += part[(size_t)(g + 32) * D + col];
-            s2 += part[(size_t)(g + 64) * D + col];
-            s3 += part[(size_t)(g + 96) * D + col];
-        }
-        for (; g < n_parts; g += 32) s0 += part[(size_t)g * D + col];
-    }
-    sm[sl][c] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (sl == 0 && col < D) {
-        float t = sm[0][c];
-#pragma unroll
-        for (int k = 1; k < 32; ++k) t += sm[k][c];
-        out[col] = t;
-    }
-}
-
 // Partial rows of the pullback: every group gets >= 4 rows of the longer tensor when there are that many, at most kQknrCap
 // workgroups (4 per CU: what the pullback's ~116 VGPRs per lane keep resident, one round).  The workspace is sized for the
 // narrowest workgroup (4 rows).
@@ -267,11 +226,6 @@ size_t qknr_bwd_ws_bytes(const nnop_qknr_desc& d) {
     return (size_t)qknr_parts(bl * d.qh, bl * d.kh, 4) * 2 * (size_t)d.dim * sizeof(float);
 }
 
-static inline bool aligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t u = 0;
-    for (const void* q : ptrs) u |= reinterpret_cast<uintptr_t>(q);
-    return (u & 15) == 0;
-}
 // lanes per row of the 16-byte path, 0 where D has none
 static inline int qknr_lpr(int D) {
     const int n = D / 16;
@@ -296,9 +250,9 @@ template <typename T, typename W, typename CS> static int launch_qknr_t(QknrPara
         NNOP_QKNR_CASE(0)
     }
 #undef NNOP_QKNR_CASE
-    if (bwd)
-        hipLaunchKernelGGL(qknr_fold_kernel, dim3((unsigned)((p.D + 31) / 32), 2), dim3(1024), 0, s, dwq, dwk,
-                           (const float*)p.part, p.n_parts, p.D);
+    if (bwd)                                                        // dwq from q's partial rows, dwk from k's behind them
+        hipLaunchKernelGGL((fold_partial_rows_kernel<float>), dim3((unsigned)((p.D + 31) / 32), 2), dim3(1024), 0, s, dwq, dwk,
+                           (const float*)p.part, (const float*)p.part + (size_t)p.n_parts * p.D, p.n_parts, p.D);
     return hipGetLastError() == hipSuccess ? NNOP_OK : NNOP_ERR_HIP;
 }
 
@@ -308,17 +262,11 @@ static int launch_qknr(const nnop_qknr_desc& d, QknrParams p, bool bwd, float* d
     p.rows_q = (long long)d.batch * d.qh * d.seq;
     p.rows_k = (long long)d.batch * d.kh * d.seq;
     p.n_parts = 0;
-    const bool w32 = d.w_dtype == NNOP_F32, cs32 = d.cs_dtype == NNOP_F32;
-    switch (d.dtype) {
-        case NNOP_F32: return launch_qknr_t<float, float, float>(p, bwd, dwq, dwk, s);
-        case NNOP_F16:
-            if (w32) return cs32 ? launch_qknr_t<_Float16, float, float>(p, bwd, dwq, dwk, s) : launch_qknr_t<_Float16, float, _Float16>(p, bwd, dwq, dwk, s);
-            return cs32 ? launch_qknr_t<_Float16, _Float16, float>(p, bwd, dwq, dwk, s) : launch_qknr_t<_Float16, _Float16, _Float16>(p, bwd, dwq, dwk, s);
-        case NNOP_BF16:
-            if (w32) return cs32 ? launch_qknr_t<__bf16, float, float>(p, bwd, dwq, dwk, s) : launch_qknr_t<__bf16, float, __bf16>(p, bwd, dwq, dwk, s);
-            return cs32 ? launch_qknr_t<__bf16, __bf16, float>(p, bwd, dwq, dwk, s) : launch_qknr_t<__bf16, __bf16, __bf16>(p, bwd, dwq, dwk, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype_side(d.dtype, d.w_dtype, [&](auto t, auto w) {
+        using T = typename decltype(t)::type;
+        using W = typename decltype(w)::type;
+        return d.cs_dtype == NNOP_F32 ? launch_qknr_t<T, W, float>(p, bwd, dwq, dwk, s) : launch_qknr_t<T, W, T>(p, bwd, dwq, dwk, s);
+    });
 }
 
 int launch_qknr_fwd(const nnop_qknr_desc& d, void* qo, void* ko, const void* q, const void* k, const void* wq, const void* wk,

@@ -8,6 +8,7 @@
 // Bound: HBM -- q, k read once + written once (+ the D/2-wide cos/sin rows).
 #include "fa_common.hpp"
 #include "fa_launch.hpp"
+#include "host_common.hpp"
 
 namespace nnop {
 
@@ -112,10 +113,7 @@ static int launch_rope_t(RopeParams p, hipStream_t s) {
     const int half = p.D >> 1;
     // the vector path issues 16-byte loads / stores: every tensor must be 16-byte aligned (rows then are, since
     // D % 16 == 0 there); an offset view from a C or Julia caller takes the element-wise kernel instead
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p.q) | reinterpret_cast<uintptr_t>(p.k) |
-                           reinterpret_cast<uintptr_t>(p.qo) | reinterpret_cast<uintptr_t>(p.ko) |
-                           reinterpret_cast<uintptr_t>(p.cos) | reinterpret_cast<uintptr_t>(p.sin)) & 15) == 0;
-    const bool vec = (half % 8) == 0 && aligned;
+    const bool vec = (half % 8) == 0 && aligned16({p.q, p.k, p.qo, p.ko, p.cos, p.sin});
     const long long cpr = vec ? half / 8 : half;
     p.n_items_q = (long long)p.B * ((p.QH + HG - 1) / HG) * p.L * cpr;
     p.n_items = p.n_items_q + (long long)p.B * ((p.KH + HG - 1) / HG) * p.L * cpr;
@@ -133,13 +131,9 @@ int launch_rope(const nnop_rope_desc& d, void* qo, void* ko, const void* q, cons
     p.D = d.dim; p.L = d.seq; p.QH = d.qh; p.KH = d.kh; p.B = d.batch;
     p.sin_sign = sin_sign;
     p.n_items_q = p.n_items = 0;                                 // set per instantiation in launch_rope_t
-    const bool cs32 = d.cs_dtype == NNOP_F32;
-    switch (d.dtype) {
-        case NNOP_F32:  return launch_rope_t<float, float>(p, s);
-        case NNOP_F16:  return cs32 ? launch_rope_t<_Float16, float>(p, s) : launch_rope_t<_Float16, _Float16>(p, s);
-        case NNOP_BF16: return cs32 ? launch_rope_t<__bf16, float>(p, s) : launch_rope_t<__bf16, __bf16>(p, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype_side(d.dtype, d.cs_dtype, [&](auto t, auto cs) {
+        return launch_rope_t<typename decltype(t)::type, typename decltype(cs)::type>(p, s);
+    });
 }
 
 }  // namespace nnop

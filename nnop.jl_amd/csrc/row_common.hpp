@@ -1,4 +1,5 @@
-// row_common.hpp -- building blocks of the row-wise HBM-streaming operators (softmax, RMSNorm, LayerNorm).
+// row_common.hpp -- building blocks of the row-wise HBM-streaming operators (softmax, the norms, GLU, cross-entropy, QK-norm +
+// RoPE, the MoE gate), shared by the three libraries as header-only code.
 //
 //  * group reduce: the gfx950 counterpart of NNop's `@groupreduce op val` (src/groupreduce.jl:13-43), which folds a
 //    workgroup's values through an LDS array in log2(groupsize) barrier-separated steps.  Here a wave folds its 64
@@ -9,9 +10,14 @@
 //    workgroup per row) as C 16-byte chunks per lane, chunk j of lane l covering elements [(j*G + l)*VEC, +VEC): every
 //    load/store instruction of a wave is one contiguous 1 KiB segment, and x is read from HBM exactly once (the
 //    reference kernels re-read the row for every pass: src/softmax.jl:35-57, src/layer_norm.jl:24-62).
+//  * group_sum: the butterfly over a sub-wave group of lanes (several rows per wave).
+//  * round_store: the one rounding on store, behind a fence that keeps the fp32 value apart from the conversion.
+//  * fold_partial_rows_kernel: the fixed-order sum of the partial rows a persistent pullback leaves (dw, db).
+// The launchers' host-side helpers (dtype dispatch, 16-byte test) are host_common.hpp's.
 #pragma once
 #include <type_traits>
 #include "fa_common.hpp"
+#include "host_common.hpp"
 
 namespace nnop {
 
@@ -59,6 +65,17 @@ template <int STEP> NNOP_DEV Sum2 fold(Sum2 v, int) { return Sum2{v.a + xlane<ST
 template <typename V, typename OP> NNOP_DEV V wave_allreduce(V v, OP op) {
     v = fold<1>(v, op); v = fold<2>(v, op); v = fold<4>(v, op);
     v = fold<8>(v, op); v = fold<16>(v, op); v = fold<32>(v, op);
+    return v;
+}
+
+// sum over an aligned group of G = 2^k <= 64 lanes of a wave, result in every lane of the group (G = 64: wave_allreduce with SumOp)
+template <int G> NNOP_DEV float group_sum(float v) {
+    if constexpr (G > 1) v += xlane<1>(v);
+    if constexpr (G > 2) v += xlane<2>(v);
+    if constexpr (G > 4) v += xlane<4>(v);
+    if constexpr (G > 8) v += xlane<8>(v);
+    if constexpr (G > 16) v += xlane<16>(v);
+    if constexpr (G > 32) v += xlane<32>(v);
     return v;
 }
 
@@ -162,6 +179,50 @@ template <typename T, typename F> static inline bool dispatch_row_shape_narrow(l
 template <typename R> NNOP_DEV void repack(R& r) {
 #pragma unroll
     for (int j = 0; j < (int)(sizeof(r.raw) / sizeof(r.raw[0])); ++j) asm volatile("" : "+v"(r.raw[j]));
+}
+
+// The one rounding on store, of an fp32 value that EXISTS: without the fence the compiler folds the last fp32 multiply and the
+// conversion to fp16 into one v_fma_mixlo_f16 (a single rounding of the exact product) on an element-wise path, while a 16-byte
+// path multiplies in fp32 and converts pairs (v_cvt_pk_f16_f32) -- two roundings, and about one result in 2^13 differs between
+// the paths.  The fence (fa_common.hpp `landed`: an empty statement, no instruction) keeps the product in fp32, so an operator's
+// vector and element paths round alike.
+template <typename T> NNOP_DEV T round_store(float x) {
+    landed(x);
+    return from_f32<T>(x);
+}
+
+// ---- partial rows of a persistent pullback -----------------------------------------------------------------------
+// out_w[e] (blockIdx.y = 0) / out_b[e] (blockIdx.y = 1) = sum over the n_parts partial rows of part_w / part_b in a fixed order:
+// a workgroup takes 32 columns x 32 slices of rows (four independent accumulators per lane keep loads in flight), slices meet
+// through LDS.  Grid (ceil(emb / 32), 1 or 2), 1024 lanes.
+template <typename O>
+__global__ __launch_bounds__(1024) void fold_partial_rows_kernel(O* __restrict__ out_w, O* __restrict__ out_b,
+                                                                  const float* __restrict__ part_w,
+                                                                  const float* __restrict__ part_b, int n_parts, int emb) {
+    __shared__ float sm[32][33];
+    const float* __restrict__ part = blockIdx.y ? part_b : part_w;
+    O* __restrict__ out = blockIdx.y ? out_b : out_w;
+    const int c = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    const int col = blockIdx.x * 32 + c;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (col < emb) {
+        int g = sl;
+        for (; g + 96 < n_parts; g += 128) {
+            s0 += part[(size_t)g * emb + col];
+            s1 += part[(size_t)(g + 32) * emb + col];
+            s2 += part[(size_t)(g + 64) * emb + col];
+            s3 += part[(size_t)(g + 96) * emb + col];
+        }
+        for (; g < n_parts; g += 32) s0 += part[(size_t)g * emb + col];
+    }
+    sm[sl][c] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (sl == 0 && col < emb) {
+        float t = sm[0][c];
+#pragma unroll
+        for (int k = 1; k < 32; ++k) t += sm[k][c];
+        out[col] = from_f32<O>(t);
+    }
 }
 
 }  // namespace nnop

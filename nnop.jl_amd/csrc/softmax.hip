@@ -131,7 +131,7 @@ __global__ __launch_bounds__(1024) void softmax_generic_kernel(const SoftmaxPara
 template <typename T, bool BWD>
 static int launch_softmax_t(const SoftmaxParams& p, hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    const bool aligned = (((uintptr_t)p.out | (uintptr_t)p.a | (uintptr_t)p.b) & 15) == 0;
+    const bool aligned = aligned16({p.out, p.a, p.b});
     bool done = false;
     if (aligned)
         done = dispatch_row_shape<T, BWD ? 2 : 1>(p.N, [&](auto shape) {
@@ -152,12 +152,10 @@ static int launch_softmax_t(const SoftmaxParams& p, hipStream_t s) {
 int launch_softmax(const nnop_softmax_desc& d, void* out, const void* a, const void* b, bool bwd, hipStream_t s) {
     SoftmaxParams p{out, a, b, d.n, d.batch};
     if (d.batch > 0x7fffffffLL) return NNOP_ERR_SHAPE;
-    switch (d.dtype) {
-        case NNOP_F32:  return bwd ? launch_softmax_t<float, true>(p, s) : launch_softmax_t<float, false>(p, s);
-        case NNOP_F16:  return bwd ? launch_softmax_t<_Float16, true>(p, s) : launch_softmax_t<_Float16, false>(p, s);
-        case NNOP_BF16: return bwd ? launch_softmax_t<__bf16, true>(p, s) : launch_softmax_t<__bf16, false>(p, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d.dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return bwd ? launch_softmax_t<T, true>(p, s) : launch_softmax_t<T, false>(p, s);
+    });
 }
 
 }  // namespace nnop

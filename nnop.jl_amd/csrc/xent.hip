@@ -176,12 +176,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const XentParams p, const
 }
 
 // ---- pullback ---------------------------------------------------------------------------------------------------------
-// The one rounding on store, of an fp32 value that exists (glu.hip glu_round): the vector and the element path round alike.
-template <typename T> NNOP_DEV T xent_round(float f) {
-    landed(f);
-    return from_f32<T>(f);
-}
-
+// Every element is stored through round_store (row_common.hpp): the vector and the element path round alike.
 // dx may be x itself: a lane reads its chunks before it writes them, and no lane touches another lane's chunk -- hence no
 // __restrict__ on either.
 template <typename T, int VEC, int G, bool CAP>
@@ -227,7 +222,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const XentParams p, const
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             if constexpr (CAP) f[i] *= __builtin_fmaf(-th[i], th[i], 1.f);
-            o[i] = xent_round<T>(f[i]);
+            o[i] = round_store<T>(f[i]);
         }
         *reinterpret_cast<tv*>(dx + (size_t)cc * VEC) = o;
     };
@@ -255,7 +250,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const XentParams p, const
             float f = elem(to_f32(x[e]), th);
             if ((unsigned)e == t.tu) f -= Gt;
             if constexpr (CAP) f *= __builtin_fmaf(-th, th, 1.f);
-            dx[e] = xent_round<T>(f);
+            dx[e] = round_store<T>(f);
         }
     }
 }
@@ -281,8 +276,7 @@ template <typename T, bool BWD> static int launch_xent_t(const XentParams& p, lo
     constexpr int V = 16 / (int)sizeof(T);
     // the vector path issues 16-byte accesses at multiples of V elements from every row start: bases 16-byte aligned and the
     // strides multiples of V (a padded vocabulary: n = 50257, ld = 50304).  Odd strides and offset views take single elements.
-    const uintptr_t bases = reinterpret_cast<uintptr_t>(p.x) | (BWD ? reinterpret_cast<uintptr_t>(p.dx) : 0);
-    const bool vec = (bases & 15) == 0 && p.ld % V == 0 && (!BWD || p.ld_grad % V == 0);
+    const bool vec = aligned16({p.x, BWD ? p.dx : nullptr}) && p.ld % V == 0 && (!BWD || p.ld_grad % V == 0);
     const bool wg = xent_workgroup_per_row(p.n, sizeof(T));
     if (vec) {
         if (wg) launch_xent_form<T, V, 256, BWD>(p, rows, s);
@@ -303,12 +297,7 @@ template <bool BWD> static int launch_xent_any(const nnop_xent_desc& d, XentPara
     p.eps = d.label_smoothing; p.zeta = d.z_loss; p.cap = d.softcap;
     p.ka = d.softcap != 0.f ? softcap_k(1.0, d.softcap).ka : 0.f;
     p.inv_n = (float)(1.0 / (double)d.n);
-    switch (d.dtype) {
-        case NNOP_F32:  return launch_xent_t<float, BWD>(p, d.rows, s);
-        case NNOP_F16:  return launch_xent_t<_Float16, BWD>(p, d.rows, s);
-        case NNOP_BF16: return launch_xent_t<__bf16, BWD>(p, d.rows, s);
-    }
-    return NNOP_ERR_DTYPE;
+    return dispatch_dtype(d.dtype, [&](auto t) { return launch_xent_t<typename decltype(t)::type, BWD>(p, d.rows, s); });
 }
 
 int launch_xent(const nnop_xent_desc& d, float* loss, float* lse, const void* logits, const void* targets, hipStream_t s) {

@@ -169,6 +169,30 @@ def test_multi_partial_fold_is_within_the_gate_and_deterministic(pkg, dt):
         assert torch.equal(a, b)
 
 
+def _partials(rows_q, rows_k, lanes_per_row):
+    """csrc/qk_norm_rope.hip qknr_parts: a workgroup of 256 / lanes_per_row groups per partial row, four rows of the longer tensor per group"""
+    per_partial = 4 * (256 // lanes_per_row)
+    return min(1024, max(1, -(-max(rows_q, rows_k) // per_partial)))
+
+
+@pytest.mark.parametrize("B,QH,KH,L,D,dt,lanes_per_row,parts", [(1, 3, 1, 700, 6, "f32", 64, 132), (2, 4, 1, 4129, 64, "bf16", 4, 130)],
+                         ids=["element-path-132-partials", "16-byte-path-130-partials"])
+def test_fold_of_more_than_128_partials_is_within_the_gate_and_deterministic(pkg, B, QH, KH, L, D, dt, lanes_per_row, parts):
+    """The fold kernel (csrc/row_common.hpp fold_partial_rows_kernel) sums slices of 32 partial rows with four accumulators while more
+    than 96 rows are ahead, then one by one: more than 128 partials, no multiple of 128, reach both loops.  k has fewer head rows than q
+    and as many partial rows, the last ones all zero.  The second base of the fold (k's partials) is computed on the host."""
+    rows_q, rows_k = B * QH * L, B * KH * L
+    assert _partials(rows_q, rows_k, lanes_per_row) == parts and parts > 128 and parts % 128 != 0 and rows_k < rows_q
+    t, got = _case(pkg, f"fold{parts}", 31, B, QH, KH, L, D, dt, offset=1.0)
+    if lanes_per_row == 64:          # the library sizes the workspace by the same rule for the narrowest workgroup: the element path's
+        import ctypes as C
+        d = pkg.qknorm._desc(t["q"], t["k"], t["wq"], t["cos"], EPS, 1.0)
+        assert pkg._lib_ext.load().nnop_qk_norm_rope_bwd_workspace_bytes(C.byref(d)) == parts * 2 * D * 4
+    again = _both(pkg, t, 1.0)
+    for a, b in zip(got, again):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("D", [128, 96])
 def test_nan_prefilled_workspace_and_outputs_change_nothing(pkg, D):
     B, QH, KH, L = 2, 5, 1, 257
