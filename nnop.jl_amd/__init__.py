@@ -5,7 +5,8 @@ Holds only what the hot path needs: ``csrc/`` (hand-written gfx950 HIP kernels +
 Llama rotary embedding applied to q, k right before attention -- SURVEY.md section 8(f) rank 2; ``softmax.py``, ``norms.py``,
 ``activations.py`` for the MLP's gated activation, ``losses.py`` for the cross-entropy over the LM head's logits and
 ``qknorm.py`` for the fused QK-norm + RoPE of the extension library, ``include/nnop_hip_ext.h``, ``moe.py`` for the
-mixture-of-experts gate and dispatch plan of the third library, ``include/nnop_hip_moe.h``), the
+mixture-of-experts gate and dispatch plan of the third library, ``include/nnop_hip_moe.h``, ``moe_data.py`` for the token
+permute and weighted combine of the fourth, ``include/nnop_hip_moe_data.h``), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -24,7 +25,9 @@ from .losses import cross_entropy, _cross_entropy, grad_cross_entropy
 from .qknorm import qk_norm_rope, _qk_norm_rope, grad_qk_norm_rope, qk_norm_rope_into, grad_qk_norm_rope_into
 from .moe import (moe_router, _moe_router, grad_moe_router, moe_router_into, grad_moe_router_into, moe_dispatch_plan,
                   moe_dispatch_plan_into)
-from . import _lib, _lib_ext, _lib_moe, activations, losses, moe, qknorm, shard, workmodel
+from .moe_data import (moe_permute, _moe_permute, grad_moe_permute, moe_permute_into, grad_moe_permute_into, moe_combine, _moe_combine,
+                       grad_moe_combine, moe_combine_into, grad_moe_combine_into)
+from . import _lib, _lib_ext, _lib_moe, _lib_moe_data, activations, losses, moe, moe_data, qknorm, shard, workmodel
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -36,5 +39,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "qk_norm_rope", "_qk_norm_rope", "grad_qk_norm_rope", "qk_norm_rope_into", "grad_qk_norm_rope_into", "qknorm",
            "moe_router", "_moe_router", "grad_moe_router", "moe_router_into", "grad_moe_router_into", "moe_dispatch_plan",
            "moe_dispatch_plan_into", "moe",
-           "shard", "workmodel", "_lib", "_lib_ext", "_lib_moe"]
+           "moe_permute", "_moe_permute", "grad_moe_permute", "moe_permute_into", "grad_moe_permute_into", "moe_combine", "_moe_combine",
+           "grad_moe_combine", "moe_combine_into", "grad_moe_combine_into", "moe_data",
+           "shard", "workmodel", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data"]
 __version__ = "0.1.0"
