@@ -1,7 +1,7 @@
 /*
  * nnop_hip_moe_data.h -- C ABI of libnnop_hip_moe_data.so: the data movement of a mixture-of-experts layer, the token permute in front
  * of the expert GEMMs and the weighted combine behind them, each with its pullback.  They consume the plan of nnop_moe_plan
- * (nnop_hip_moe.h); the expert GEMMs themselves (a grouped GEMM) are not part of the library.
+ * (nnop_hip_moe.h); the expert GEMMs between them (a grouped GEMM over the plan's offsets) are the fifth library's, nnop_hip_moe_gemm.h.
  *
  * A fourth library beside libnnop_hip.so (nnop_hip.h), libnnop_hip_ext.so (nnop_hip_ext.h) and libnnop_hip_moe.so (nnop_hip_moe.h),
  * built the same way as the second and third: an ABI version of its own, nothing linked from the other three, only this header's

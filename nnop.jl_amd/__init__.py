@@ -6,7 +6,8 @@ Llama rotary embedding applied to q, k right before attention -- SURVEY.md secti
 ``activations.py`` for the MLP's gated activation, ``losses.py`` for the cross-entropy over the LM head's logits and
 ``qknorm.py`` for the fused QK-norm + RoPE of the extension library, ``include/nnop_hip_ext.h``, ``moe.py`` for the
 mixture-of-experts gate and dispatch plan of the third library, ``include/nnop_hip_moe.h``, ``moe_data.py`` for the token
-permute and weighted combine of the fourth, ``include/nnop_hip_moe_data.h``), the
+permute and weighted combine of the fourth, ``include/nnop_hip_moe_data.h``, ``moe_gemm.py`` for the grouped expert GEMM of
+the fifth, ``include/nnop_hip_moe_gemm.h``), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -27,7 +28,10 @@ from .moe import (moe_router, _moe_router, grad_moe_router, moe_router_into, gra
                   moe_dispatch_plan_into)
 from .moe_data import (moe_permute, _moe_permute, grad_moe_permute, moe_permute_into, grad_moe_permute_into, moe_combine, _moe_combine,
                        grad_moe_combine, moe_combine_into, grad_moe_combine_into)
-from . import _lib, _lib_ext, _lib_moe, _lib_moe_data, activations, losses, moe, moe_data, qknorm, shard, workmodel
+from .moe_gemm import (moe_grouped_gemm, _moe_grouped_gemm, grad_moe_grouped_gemm, moe_grouped_gemm_into,
+                       grad_moe_grouped_gemm_x_into, grad_moe_grouped_gemm_w_into)
+from . import (_lib, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, activations, losses, moe, moe_data, moe_gemm, qknorm, shard,
+               workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -41,5 +45,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "moe_dispatch_plan_into", "moe",
            "moe_permute", "_moe_permute", "grad_moe_permute", "moe_permute_into", "grad_moe_permute_into", "moe_combine", "_moe_combine",
            "grad_moe_combine", "moe_combine_into", "grad_moe_combine_into", "moe_data",
-           "shard", "workmodel", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data"]
+           "moe_grouped_gemm", "_moe_grouped_gemm", "grad_moe_grouped_gemm", "moe_grouped_gemm_into", "grad_moe_grouped_gemm_x_into",
+           "grad_moe_grouped_gemm_w_into", "moe_gemm",
+           "shard", "workmodel", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm"]
 __version__ = "0.1.0"
