@@ -2,13 +2,15 @@
 
 This is the same binding, call for call, that the Julia extension in ``julia/NNopHIPExt.jl``
 makes with ``ccall``.  There is NO fallback: if the shared library is missing or a symbol is
-absent the import of the product path raises.
+absent the import of the product path raises.  ``load_library`` is the load sequence of this binding and of the four
+side bindings (``_lib_ext``, ``_lib_moe``, ``_lib_moe_data``, ``_lib_moe_gemm``).
 """
 from __future__ import annotations
 
 import ctypes as C
 import numbers
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NNOP_LIB_PATH: development override (timing-only ablation builds); never set in production
@@ -35,43 +37,7 @@ NNOP_ERR_HIP = -10
 NNOP_ERR_ALIGN = -11
 NNOP_ERR_OPTS = -12
 
-EXPORTED_SYMBOLS = (
-    "nnop_fa_fwd",
-    "nnop_fa_bwd_workspace_bytes",
-    "nnop_fa_bwd_workspace_bytes_pair",
-    "nnop_fa_bwd",
-    "nnop_fa_fwd_ex",
-    "nnop_fa_bwd_ex",
-    "nnop_fa_fwd_sinks",
-    "nnop_fa_bwd_sinks",
-    "nnop_fa_fwd_softcap",
-    "nnop_fa_bwd_softcap",
-    "nnop_llama_rope",
-    "nnop_online_softmax",
-    "nnop_online_softmax_bwd",
-    "nnop_rms_norm",
-    "nnop_rms_norm_bwd",
-    "nnop_layer_norm",
-    "nnop_layer_norm_bwd",
-    "nnop_norm_bwd_workspace_bytes",
-    "nnop_add_rms_norm",
-    "nnop_add_rms_norm_bwd",
-    "nnop_add_layer_norm",
-    "nnop_add_layer_norm_bwd",
-    "nnop_glu",
-    "nnop_glu_bwd",
-    "nnop_cross_entropy",
-    "nnop_cross_entropy_bwd",
-    "nnop_fa_shards",
-    "nnop_shared_memory",
-    "nnop_strerror",
-    "nnop_abi_version",
-)
-
-
-# Test-only hooks (csrc/nnop_debug.h): exported by the library, deliberately NOT in the public header.
-DEBUG_SYMBOLS = ("nnop_debug_set", "nnop_debug_dev_build", "nnop_debug_fwd_form", "nnop_debug_bwd_form",
-                 "nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex", "nnop_debug_fwd_form_cap", "nnop_debug_bwd_form_cap")
+# what the test-only hooks (csrc/nnop_debug.h; DEBUG_PROTOTYPES below) report and take
 FWD_FORMS = {0: "fa_fwd_kernel", 1: "fa_fwd_split_kernel", 2: "fa_fwd_w64_kernel", 3: "fa_fwd_generic_kernel", 4: "fa_fwd_duo_kernel"}
 FWD_FORMS_CAP = {0: "fa_fwd_cap_kernel", 3: "fa_fwd_generic_cap_kernel"}      # a capped call runs these two forms only; form names, not symbols (fwd_form)
 # keys of nnop_debug_set == enum TuneKey (csrc/tuning.hpp)
@@ -143,115 +109,99 @@ class NNopLibraryMissing(ImportError):
     pass
 
 
+_vp = _u8p = C.c_void_p
+_fd, _op, _nd, _gd, _xd = C.POINTER(FaDesc), C.POINTER(FaOpts), C.POINTER(NormDesc), C.POINTER(GluDesc), C.POINTER(XentDesc)
+
+# name -> (restype, argtypes) of every function of include/nnop_hip.h.  load() declares them from this table and refuses a library
+# that lacks one; EXPORTED_SYMBOLS is its keys, so the symbol list and the prototypes cannot drift apart.
+PROTOTYPES = {
+    "nnop_fa_fwd": (C.c_int, [_fd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp]),
+    "nnop_fa_bwd_workspace_bytes": (C.c_size_t, [_fd]),
+    "nnop_fa_bwd_workspace_bytes_pair": (C.c_size_t, [_fd]),
+    "nnop_fa_bwd": (C.c_int, [_fd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp, C.c_size_t, _vp]),
+    "nnop_fa_fwd_ex": (C.c_int, [_fd, _op, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp]),
+    "nnop_fa_bwd_ex": (C.c_int, [_fd, _op, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp, C.c_size_t, _vp]),
+    "nnop_fa_fwd_sinks": (C.c_int, [_fd, _op, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp]),
+    "nnop_fa_bwd_sinks": (C.c_int, [_fd, _op, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp,
+                                    C.c_size_t, _vp]),
+    "nnop_fa_fwd_softcap": (C.c_int, [_fd, _op, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p, _vp]),
+    "nnop_fa_bwd_softcap": (C.c_int, [_fd, _op, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u8p,
+                                      _vp, C.c_size_t, _vp]),
+    "nnop_llama_rope": (C.c_int, [C.POINTER(RopeDesc), _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp]),
+    "nnop_online_softmax": (C.c_int, [C.POINTER(SoftmaxDesc), _vp, _vp, _vp]),
+    "nnop_online_softmax_bwd": (C.c_int, [C.POINTER(SoftmaxDesc), _vp, _vp, _vp, _vp]),
+    "nnop_rms_norm": (C.c_int, [_nd, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp]),
+    "nnop_rms_norm_bwd": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_size_t, _vp]),
+    "nnop_layer_norm": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp]),
+    "nnop_layer_norm_bwd": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "nnop_norm_bwd_workspace_bytes": (C.c_size_t, [_nd, C.c_int]),
+    "nnop_add_rms_norm": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp]),
+    "nnop_add_rms_norm_bwd": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_size_t, _vp]),
+    "nnop_add_layer_norm": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp]),
+    "nnop_add_layer_norm_bwd": (C.c_int, [_nd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "nnop_glu": (C.c_int, [_gd, _vp, _vp, _vp, _vp]),
+    "nnop_glu_bwd": (C.c_int, [_gd, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nnop_cross_entropy": (C.c_int, [_xd, _vp, _vp, _vp, _vp, _vp]),
+    "nnop_cross_entropy_bwd": (C.c_int, [_xd, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nnop_fa_shards": (C.c_int, [_fd, C.c_int, C.c_int, C.POINTER(FaShard)]),
+    "nnop_shared_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
+    "nnop_strerror": (C.c_char_p, [C.c_int]),
+    "nnop_abi_version": (C.c_int, []),
+}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+# Test-only hooks (csrc/nnop_debug.h): exported by the library, deliberately NOT in the public header and not part of the ABI;
+# each is bound only when the library carries it.
+DEBUG_PROTOTYPES = {
+    "nnop_debug_set": (C.c_int, [C.c_int, C.c_int]),
+    "nnop_debug_dev_build": (C.c_int, []),
+    "nnop_debug_fwd_form": (C.c_int, [_fd, C.c_int, C.c_int]),
+    "nnop_debug_bwd_form": (C.c_int, [_fd, C.c_int, C.c_int]),
+    "nnop_debug_fwd_form_ex": (C.c_int, [_fd, _op, C.c_int, C.c_int]),
+    "nnop_debug_bwd_form_ex": (C.c_int, [_fd, _op, C.c_int, C.c_int]),
+    "nnop_debug_fwd_form_cap": (C.c_int, [_fd, _op, C.c_float, C.c_int, C.c_int]),
+    "nnop_debug_bwd_form_cap": (C.c_int, [_fd, _op, C.c_float, C.c_int, C.c_int]),
+}
+DEBUG_SYMBOLS = tuple(DEBUG_PROTOTYPES)
+
+
+def load_library(binding, label, version_name, version_symbol, optional=None):
+    """The load sequence of all five bindings.  `binding` is the binding module: its LIB_PATH, EXPORTED_SYMBOLS, PROTOTYPES and version
+    constant (`version_name`) are read now, not at import, and the library lands in its `_lib`.  dlopen, compare what `version_symbol`
+    returns first -- a stale library may lack symbols the binding declares -- then require every exported symbol and declare the
+    prototypes; those of `optional` only where the library has the symbol.  `label` names the version in the message."""
+    path, rebuild = binding.LIB_PATH, "rebuild with `make -C nnop.jl_amd/csrc -j8`"
+    if not os.path.exists(path):
+        raise NNopLibraryMissing(
+            f"{path} not found: build it with `make -C nnop.jl_amd/csrc -j8` "
+            "(or __graft_entry__.build()).  There is no CPU or PyTorch fallback.")
+    lib = C.CDLL(path)
+    if not hasattr(lib, version_symbol):
+        raise NNopLibraryMissing(f"{path} exports no {version_symbol}: {rebuild}")
+    version, wanted = getattr(lib, version_symbol), getattr(binding, version_name)
+    version.restype, version.argtypes = C.c_int, []
+    if version() != wanted:
+        raise NNopLibraryMissing(f"{path} has {label} {version()}, this binding needs {wanted}: {rebuild}")
+    for name in binding.EXPORTED_SYMBOLS:
+        if not hasattr(lib, name):
+            raise NNopLibraryMissing(f"{path} does not export {name}: {rebuild}")
+    prototypes = dict(binding.PROTOTYPES)
+    prototypes.update((name, proto) for name, proto in (optional or {}).items() if hasattr(lib, name))
+    for name, (restype, argtypes) in prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    binding._lib = lib
+    return lib
+
+
 _lib = None
 
 
 def load():
     """dlopen the library once and declare the prototypes.  Raises loudly when absent."""
-    global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NNopLibraryMissing(
-            f"{LIB_PATH} not found: build it with `make -C nnop.jl_amd/csrc -j8` "
-            "(or __graft_entry__.build()).  There is no CPU or PyTorch fallback.")
-    lib = C.CDLL(LIB_PATH)
-    # the version first: a stale library may lack symbols this binding declares below (a bare AttributeError otherwise)
-    if not hasattr(lib, "nnop_abi_version"):
-        raise NNopLibraryMissing(f"{LIB_PATH} exports no nnop_abi_version: rebuild with `make -C nnop.jl_amd/csrc -j8`")
-    lib.nnop_abi_version.restype = C.c_int
-    lib.nnop_abi_version.argtypes = []
-    if lib.nnop_abi_version() != ABI_VERSION:
-        raise NNopLibraryMissing(f"{LIB_PATH} has ABI version {lib.nnop_abi_version()}, this binding needs "
-                                 f"{ABI_VERSION}: rebuild with `make -C nnop.jl_amd/csrc -j8`")
-    vp, u8p = C.c_void_p, C.c_void_p
-    lib.nnop_fa_fwd.restype = C.c_int
-    lib.nnop_fa_fwd.argtypes = [C.POINTER(FaDesc), vp, vp, vp, vp, vp, vp, vp, u8p, vp]
-    lib.nnop_fa_bwd_workspace_bytes.restype = C.c_size_t
-    lib.nnop_fa_bwd_workspace_bytes.argtypes = [C.POINTER(FaDesc)]
-    lib.nnop_fa_bwd_workspace_bytes_pair.restype = C.c_size_t
-    lib.nnop_fa_bwd_workspace_bytes_pair.argtypes = [C.POINTER(FaDesc)]
-    lib.nnop_fa_bwd.restype = C.c_int
-    lib.nnop_fa_bwd.argtypes = [C.POINTER(FaDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                u8p, vp, C.c_size_t, vp]
-    op = C.POINTER(FaOpts)
-    lib.nnop_fa_fwd_ex.restype = C.c_int
-    lib.nnop_fa_fwd_ex.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
-    lib.nnop_fa_bwd_ex.restype = C.c_int
-    lib.nnop_fa_bwd_ex.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                   u8p, vp, C.c_size_t, vp]
-    lib.nnop_fa_fwd_sinks.restype = C.c_int
-    lib.nnop_fa_fwd_sinks.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
-    lib.nnop_fa_bwd_sinks.restype = C.c_int
-    lib.nnop_fa_bwd_sinks.argtypes = [C.POINTER(FaDesc), op, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                      u8p, vp, C.c_size_t, vp]
-    lib.nnop_fa_fwd_softcap.restype = C.c_int
-    lib.nnop_fa_fwd_softcap.argtypes = [C.POINTER(FaDesc), op, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, u8p, vp]
-    lib.nnop_fa_bwd_softcap.restype = C.c_int
-    lib.nnop_fa_bwd_softcap.argtypes = [C.POINTER(FaDesc), op, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                        u8p, vp, C.c_size_t, vp]
-    lib.nnop_llama_rope.restype = C.c_int
-    lib.nnop_llama_rope.argtypes = [C.POINTER(RopeDesc), vp, vp, vp, vp, vp, vp, C.c_float, vp]
-    lib.nnop_online_softmax.restype = C.c_int
-    lib.nnop_online_softmax.argtypes = [C.POINTER(SoftmaxDesc), vp, vp, vp]
-    lib.nnop_online_softmax_bwd.restype = C.c_int
-    lib.nnop_online_softmax_bwd.argtypes = [C.POINTER(SoftmaxDesc), vp, vp, vp, vp]
-    nd = C.POINTER(NormDesc)
-    lib.nnop_rms_norm.restype = C.c_int
-    lib.nnop_rms_norm.argtypes = [nd, vp, vp, vp, vp, C.c_float, C.c_float, vp]
-    lib.nnop_rms_norm_bwd.restype = C.c_int
-    lib.nnop_rms_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, C.c_float, vp, C.c_size_t, vp]
-    lib.nnop_layer_norm.restype = C.c_int
-    lib.nnop_layer_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, C.c_float, vp]
-    lib.nnop_layer_norm_bwd.restype = C.c_int
-    lib.nnop_layer_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.nnop_norm_bwd_workspace_bytes.restype = C.c_size_t
-    lib.nnop_norm_bwd_workspace_bytes.argtypes = [nd, C.c_int]
-    lib.nnop_add_rms_norm.restype = C.c_int
-    lib.nnop_add_rms_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
-    lib.nnop_add_rms_norm_bwd.restype = C.c_int
-    lib.nnop_add_rms_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, C.c_size_t, vp]
-    lib.nnop_add_layer_norm.restype = C.c_int
-    lib.nnop_add_layer_norm.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp]
-    lib.nnop_add_layer_norm_bwd.restype = C.c_int
-    lib.nnop_add_layer_norm_bwd.argtypes = [nd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    gd = C.POINTER(GluDesc)
-    lib.nnop_glu.restype = C.c_int
-    lib.nnop_glu.argtypes = [gd, vp, vp, vp, vp]
-    lib.nnop_glu_bwd.restype = C.c_int
-    lib.nnop_glu_bwd.argtypes = [gd, vp, vp, vp, vp, vp, vp]
-    xd = C.POINTER(XentDesc)
-    lib.nnop_cross_entropy.restype = C.c_int
-    lib.nnop_cross_entropy.argtypes = [xd, vp, vp, vp, vp, vp]
-    lib.nnop_cross_entropy_bwd.restype = C.c_int
-    lib.nnop_cross_entropy_bwd.argtypes = [xd, vp, vp, vp, vp, vp, vp]
-    lib.nnop_fa_shards.restype = C.c_int
-    lib.nnop_fa_shards.argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int, C.POINTER(FaShard)]
-    lib.nnop_shared_memory.restype = C.c_int
-    lib.nnop_shared_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
-    lib.nnop_strerror.restype = C.c_char_p
-    lib.nnop_strerror.argtypes = [C.c_int]
-    # test-only hooks (csrc/nnop_debug.h): not part of the ABI, bound only when the library carries them
-    if hasattr(lib, "nnop_debug_set"):
-        lib.nnop_debug_set.restype = C.c_int
-        lib.nnop_debug_set.argtypes = [C.c_int, C.c_int]
-    if hasattr(lib, "nnop_debug_dev_build"):
-        lib.nnop_debug_dev_build.restype = C.c_int
-        lib.nnop_debug_dev_build.argtypes = []
-    for name in ("nnop_debug_fwd_form", "nnop_debug_bwd_form"):
-        if hasattr(lib, name):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.c_int, C.c_int]
-    for name in ("nnop_debug_fwd_form_ex", "nnop_debug_bwd_form_ex"):
-        if hasattr(lib, name):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.POINTER(FaOpts), C.c_int, C.c_int]
-    for name in ("nnop_debug_fwd_form_cap", "nnop_debug_bwd_form_cap"):
-        if hasattr(lib, name):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.POINTER(FaDesc), C.POINTER(FaOpts), C.c_float, C.c_int, C.c_int]
-    _lib = lib
-    return lib
+    return load_library(sys.modules[__name__], "ABI version", "ABI_VERSION", "nnop_abi_version", optional=DEBUG_PROTOTYPES)
 
 
 def strerror(status: int) -> str:

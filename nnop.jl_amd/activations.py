@@ -18,13 +18,11 @@ picks it by default.  GPU-only like every operator here.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._common import NNopError, _DTYPES, _launch
 from ._lib import GluDesc
-from .attention import NNopError, _DTYPES, _on_device, _stream
 
 __all__ = ["glu", "swiglu", "geglu", "glu_packed", "_glu", "grad_glu", "grad_glu_packed", "glu_into", "grad_glu_into"]
 
@@ -92,14 +90,6 @@ def _by_stride(gate, up):
     if lg is not None and lg == lu:
         return gate, up, lg
     return gate.contiguous(), up.contiguous(), gate.shape[-1]
-
-
-def _launch(name, d, t, *ptrs):
-    """the one place a GLU entry point is called: `ptrs` are raw addresses (0 = NULL), `t` a tensor on the target device"""
-    with _on_device(t):
-        st = getattr(_lib.load(), name)(C.byref(d), *(C.c_void_p(p) for p in ptrs), _stream(t))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
 
 
 def _desc(t, act, layout, n, ld, alpha, limit):

@@ -16,30 +16,19 @@ The Julia shim that a maintainer of the reference would load instead is
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import math
 
 import torch
 
 from . import _lib
+from ._common import NNopError, _DTYPES, _on_device, _ptr, _raise, _stream
 from ._lib import FaDesc
 
 __all__ = [
     "NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
     "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into",
 ]
-
-
-class NNopError(RuntimeError):
-    """Counterpart of the ``ErrorException`` raised by the reference's ``error(...)`` calls."""
-
-    def __init__(self, msg, status=None):
-        super().__init__(msg)
-        self.status = status
-
-
-_DTYPES = {torch.float32: _lib.NNOP_F32, torch.float16: _lib.NNOP_F16, torch.bfloat16: _lib.NNOP_BF16}
 
 
 def _jl_shape(t):
@@ -102,35 +91,10 @@ def _desc(q, k, v, causal):
                   causal=1 if causal else 0, emb_k=KE, emb_v=v.shape[3], kl_v=v.shape[2], kh_v=v.shape[1])
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-# Per-call host cost matters for launch-bound shapes (a norm over 1024 x 1024 runs 4 us on the GPU): take the raw stream
-# handle without building a torch.cuda.Stream object, and skip the device guard when the tensor's device is current.
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_NO_GUARD = contextlib.nullcontext()
-
-
-def _stream(t):
-    if _raw_stream is not None:
-        idx = t.device.index
-        return C.c_void_p(_raw_stream(torch.cuda.current_device() if idx is None else idx))
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _on_device(t):
-    """Context that makes t's device current for allocations and the launch (a no-op when it already is)."""
-    idx = t.device.index
-    return _NO_GUARD if idx is None or idx == torch.cuda.current_device() else torch.cuda.device(t.device)
-
-
 def shared_memory(device_id: int = 0) -> int:
     """``NNop._shared_memory(::ROCBackend, device_id)`` (ext/NNopAMDGPUExt.jl:6-9)."""
     out = C.c_uint64(0)
-    st = _lib.load().nnop_shared_memory(int(device_id), C.byref(out))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
+    _raise(_lib.load().nnop_shared_memory(int(device_id), C.byref(out)))
     return int(out.value)
 
 

@@ -22,14 +22,11 @@ GPU-only like every operator here.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
+from ._common import NNopError, _DTYPES, _launch, _on_device
 from ._lib import XentDesc
 from .activations import _row_stride
-from .attention import NNopError, _DTYPES, _on_device, _stream
 
 __all__ = ["cross_entropy", "_cross_entropy", "grad_cross_entropy"]
 
@@ -76,13 +73,6 @@ def _desc(t, rows, n, ld, ld_grad, targets, ignore_index, label_smoothing, z_los
     return XentDesc(dtype=_DTYPES[t.dtype], index_bytes=_INDEX[targets.dtype], rows=rows, n=n, ld=ld, ld_grad=ld_grad,
                     ignore_index=int(ignore_index), index_base=index_base, reserved=0, label_smoothing=float(label_smoothing),
                     z_loss=float(z_loss), softcap=float(softcap), reserved_f=0.0)
-
-
-def _launch(name, d, t, *ptrs):
-    with _on_device(t):
-        st = getattr(_lib.load(), name)(C.byref(d), *(C.c_void_p(p) for p in ptrs), _stream(t))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
 
 
 def _cross_entropy(logits, targets, *, ignore_index=-100, label_smoothing=0.0, z_loss=0.0, softcap=0.0):

@@ -27,16 +27,11 @@ import numbers
 import torch
 
 from . import _lib, _lib_moe
+from ._common import NNopError, _DTYPES, _dtype_name, _on_device, _ptr, _raise, _stream
 from ._lib_moe import MoePlanDesc, MoeRouterDesc, NORMS, MAX_EXPERTS, MAX_TOPK
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
 
 __all__ = ["moe_router", "_moe_router", "grad_moe_router", "moe_router_into", "grad_moe_router_into", "moe_dispatch_plan",
            "moe_dispatch_plan_into"]
-
-
-def _raise(st):
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
 
 
 def _int(name, v):
@@ -80,7 +75,7 @@ def _rows(logits, E):
 def _check_buf(name, t, shape, dtype, like):
     if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != like.device
             or not t.is_contiguous()):
-        raise NNopError(f"`{name}` must be a dense {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)} on the device of logits")
+        raise NNopError(f"`{name}` must be a dense {_dtype_name(dtype)} tensor of shape {tuple(shape)} on the device of logits")
 
 
 def _desc(logits, T, E, k, ld, norm):

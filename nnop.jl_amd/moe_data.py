@@ -26,9 +26,9 @@ import ctypes as C
 import torch
 
 from . import _lib, _lib_moe_data
+from ._common import NNopError, _DTYPES, _dtype_name, _on_device, _ptr, _raise, _stream
 from ._lib_moe_data import MoeRowsDesc, MAX_DIM, MAX_TOPK
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
-from .moe import _raise, _rows
+from .moe import _rows
 
 __all__ = ["moe_permute", "_moe_permute", "grad_moe_permute", "moe_permute_into", "grad_moe_permute_into", "moe_combine", "_moe_combine",
            "grad_moe_combine", "moe_combine_into", "grad_moe_combine_into"]
@@ -74,8 +74,8 @@ def _geometry(fn, T, k, D):
 def _same(name, t, shape, like):
     """a row array of the shape `shape`, in the dtype and on the device of `like`"""
     if tuple(t.shape) != tuple(shape) or t.dtype != like.dtype or t.device != like.device:
-        raise NNopError(f"`{name}` must be a {str(like.dtype).replace('torch.', '')} tensor of shape {tuple(shape)} on the device of the "
-                        f"other arrays, got {str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+        raise NNopError(f"`{name}` must be a {_dtype_name(like.dtype)} tensor of shape {tuple(shape)} on the device of the "
+                        f"other arrays, got {_dtype_name(t.dtype)} {tuple(t.shape)}")
 
 
 def _side(name, t, shape, like, out=False):

@@ -24,9 +24,9 @@ import ctypes as C
 import torch
 
 from . import _lib, _lib_moe_gemm
+from ._common import NNopError, _DTYPES, _dtype_name, _on_device, _ptr, _raise, _stream
 from ._lib_moe_gemm import MoeGemmDesc, MAX_DIM, MAX_EXPERTS
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
-from .moe import _raise, _rows
+from .moe import _rows
 from .moe_data import _index_array, _out_rows, _row_array, _same
 
 __all__ = ["moe_grouped_gemm", "_moe_grouped_gemm", "grad_moe_grouped_gemm", "moe_grouped_gemm_into", "grad_moe_grouped_gemm_x_into",
@@ -40,7 +40,7 @@ def _weights(fn, name, w, like):
     if w.dim() != 3:
         raise NNopError(f"`{name}` must be a tensor of shape (E, N, K), got {tuple(w.shape)}", _lib.NNOP_ERR_SHAPE)
     if w.dtype != like.dtype or w.device != like.device:
-        raise NNopError(f"`{name}` must have the element type and device of the row arrays, got {str(w.dtype).replace('torch.', '')}")
+        raise NNopError(f"`{name}` must have the element type and device of the row arrays, got {_dtype_name(w.dtype)}")
     return tuple(w.shape)
 
 

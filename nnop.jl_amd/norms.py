@@ -25,8 +25,8 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._common import NNopError, _DTYPES, _on_device, _ptr, _raise, _stream
 from ._lib import NormDesc
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
 
 __all__ = ["rms_norm", "_rms_norm", "grad_rms_norm", "layer_norm", "_layer_norm", "grad_layer_norm",
            "add_rms_norm", "_add_rms_norm", "grad_add_rms_norm", "add_layer_norm", "_add_layer_norm", "grad_add_layer_norm"]
@@ -58,11 +58,6 @@ def _check(x, w, b=None):
 
 def _desc(x, w):
     return NormDesc(dtype=_DTYPES[x.dtype], w_dtype=_DTYPES[w.dtype], emb=x.shape[1], reserved=0, n=x.shape[0])
-
-
-def _raise(st):
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
 
 
 def _workspace(d, ln, device):

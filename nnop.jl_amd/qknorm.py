@@ -21,8 +21,8 @@ import numbers
 import torch
 
 from . import _lib, _lib_ext
+from ._common import NNopError, _DTYPES, _on_device, _ptr, _raise, _stream
 from ._lib_ext import QknrDesc
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
 
 __all__ = ["qk_norm_rope", "_qk_norm_rope", "grad_qk_norm_rope", "qk_norm_rope_into", "grad_qk_norm_rope_into"]
 
@@ -75,11 +75,6 @@ def _desc(q, k, wq, cos, eps, offset):
     B, QH, L, D = q.shape
     return QknrDesc(dtype=_DTYPES[q.dtype], w_dtype=_DTYPES[wq.dtype], cs_dtype=_DTYPES[cos.dtype], dim=D, seq=L, qh=QH,
                     kh=k.shape[1], batch=B, eps=float(eps), offset=float(offset))
-
-
-def _raise(st):
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
 
 
 def _dense(*ts):

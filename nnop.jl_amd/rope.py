@@ -15,8 +15,8 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._common import NNopError, _DTYPES, _on_device, _ptr, _raise, _stream
 from ._lib import RopeDesc
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
 
 __all__ = ["LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into"]
 
@@ -81,10 +81,8 @@ def llama_rope_into(q_out, k_out, q, k, cos, sin, *, bwd: bool = False):
     B, QH, L, D = q.shape
     d = RopeDesc(dtype=_DTYPES[q.dtype], cs_dtype=_DTYPES[cos.dtype], dim=D, seq=L, qh=QH, kh=k.shape[1], batch=B)
     with _on_device(q):
-        st = _lib.load().nnop_llama_rope(C.byref(d), _ptr(q_out), _ptr(k_out), _ptr(q), _ptr(k), _ptr(cos), _ptr(sin),
-                                         C.c_float(-1.0 if bwd else 1.0), _stream(q))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
+        _raise(_lib.load().nnop_llama_rope(C.byref(d), _ptr(q_out), _ptr(k_out), _ptr(q), _ptr(k), _ptr(cos), _ptr(sin),
+                                           C.c_float(-1.0 if bwd else 1.0), _stream(q)))
     return q_out, k_out
 
 

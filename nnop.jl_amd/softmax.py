@@ -12,8 +12,8 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._common import NNopError, _DTYPES, _on_device, _ptr, _raise, _stream
 from ._lib import SoftmaxDesc
-from .attention import NNopError, _DTYPES, _on_device, _ptr, _stream
 
 __all__ = ["online_softmax", "grad_online_softmax", "online_softmax_into"]
 
@@ -42,9 +42,7 @@ def online_softmax_into(y, x):
     if y.shape != x.shape or y.dtype != x.dtype or y.device != x.device or not y.is_contiguous():
         raise NNopError("output buffer must be dense and match x in shape, dtype and device")
     with _on_device(x):
-        st = _lib.load().nnop_online_softmax(C.byref(_desc(x)), _ptr(y), _ptr(x), _stream(x))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
+        _raise(_lib.load().nnop_online_softmax(C.byref(_desc(x)), _ptr(y), _ptr(x), _stream(x)))
     return y
 
 
@@ -56,9 +54,7 @@ def grad_online_softmax(dy, y):
     dy, y = dy.contiguous(), y.contiguous()
     dx = torch.empty_like(y)
     with _on_device(y):
-        st = _lib.load().nnop_online_softmax_bwd(C.byref(_desc(y)), _ptr(dx), _ptr(dy), _ptr(y), _stream(y))
-    if st != _lib.NNOP_OK:
-        raise NNopError(_lib.strerror(st), st)
+        _raise(_lib.load().nnop_online_softmax_bwd(C.byref(_desc(y)), _ptr(dx), _ptr(dy), _ptr(y), _stream(y)))
     return dx
 
 
