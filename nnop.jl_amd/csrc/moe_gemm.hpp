@@ -8,7 +8,6 @@ namespace nnop {
 
 constexpr int kMoeGemmMaxExperts = 1024;
 constexpr int kMoeGemmMaxDim = 65536;
-constexpr int kMoeGemmTile = 128;   // BM = BN: the output tile of one workgroup
 
 // the three products of the header; the caller has checked moe_gemm_workgroups() <= 2^31 - 1
 enum MoeGemmProduct { kMoeGemmFwd = 0, kMoeGemmBwdX = 1, kMoeGemmBwdW = 2 };

@@ -1,7 +1,7 @@
 // nnop_moe_gemm_capi.cpp -- the extern "C" boundary of libnnop_hip_moe_gemm.so, declared in include/nnop_hip_moe_gemm.h.
 //
 // Every argument check happens here, in the header's order, before anything touches the device.  The library exports these four
-// functions and nothing else (nnop_moe_gemm.map); it links nothing from the other four libraries.
+// functions and nothing else (nnop_moe_gemm.map); it links nothing from the other libraries.
 #include "moe_gemm.hpp"
 #include "host_common.hpp"
 
