@@ -64,9 +64,10 @@ typedef enum nnop_status {
     NNOP_ERR_WORKSPACE      = -9,  /* workspace smaller than nnop_fa_bwd_workspace_bytes                      */
     NNOP_ERR_HIP            = -10, /* HIP runtime error at launch (hipGetLastError)                          */
     NNOP_ERR_ALIGN          = -11, /* a tensor or workspace base address is not aligned as the kernels need:
-                                      16 bytes for q, k, v, o, the gradients, pair / dpair and the workspace
+                                      16 bytes for q, k, v, o, dO, dq, dk, dv and the workspace
                                       (the MFMA kernels move them with 16-byte vector accesses and LDS-DMA),
-                                      the element size for ms, ls.  Embedding dims that run the plain-HIP
+                                      the element size for pair / dpair (a batch slice of a bias, nnop_fa_shards'
+                                      pair_off, starts at any element) and for ms, ls.  Embedding dims that run the plain-HIP
                                       kernels (not 16 / 32 / 64 / 128 / 256) need element alignment only.      */
     NNOP_ERR_OPTS           = -12  /* invalid attention options (nnop_fa_opts): a reserved field is not 0, or a window
                                       side is below -1 (ABI version 7); nnop_glu_desc: an unknown act or layout, or

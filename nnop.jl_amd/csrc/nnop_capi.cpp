@@ -55,8 +55,11 @@ static int check_desc(const nnop_fa_desc* d) {
     if ((long long)d->ql * d->emb > 0x7fffffffLL || (long long)d->kl * d->emb > 0x7fffffffLL) return NNOP_ERR_SHAPE;
     return NNOP_OK;
 }
-// Base alignment (NNOP_ERR_ALIGN): the MFMA kernels move q, k, v, o, the gradients, the bias and the workspace with 16-byte vector
+// Base alignment (NNOP_ERR_ALIGN): the MFMA kernels move q, k, v, o, the gradients and the workspace with 16-byte vector
 // accesses and LDS-DMA from the raw base; the plain-HIP kernels (embedding dims outside the tiled set) access single elements.
+// pair / dpair need the element size only: the forward and the direct backward path gather the bias element by element, the staged
+// path's pack / unpack kernels take 16-byte vectors only from a 16-byte aligned base (pair_tile.hpp), and a batch slice of a bias
+// (nnop_fa_shards: pair_off = b0 * KL * QL * QH elements) starts at any element.
 // The optional arguments (pair, dpair, sinks, dsinks) go through `misaligned` as they are: NULL counts as aligned.
 static inline size_t tensor_align(const nnop_fa_desc* d) {
     const bool tiled = emb_tiled(d->emb) || d->emb == 256;
@@ -144,7 +147,7 @@ const char* nnop_strerror(int status) {
         case NNOP_ERR_WORKSPACE: return "Backward workspace is smaller than nnop_*_bwd_workspace_bytes().";
         case NNOP_ERR_HIP: return "HIP runtime error at kernel launch.";
         case NNOP_ERR_ALIGN:
-            return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, gradients, pair and workspace; the element size for ms, ls "
+            return "A tensor or workspace base address is misaligned (16 bytes for q, k, v, o, dq, dk, dv and workspace; the element size for pair, dpair, ms, ls "
                    "and for the arrays of nnop_glu; nnop_cross_entropy: the element size for logits and dlogits, 4 bytes for loss, lse and dloss, "
                    "index_bytes for targets).";
         case NNOP_ERR_OPTS:
@@ -233,7 +236,7 @@ int nnop_fa_fwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const f
     if (pair && check_pair(d) != NNOP_OK) return NNOP_ERR_SHAPE;
     {
         const size_t ta = tensor_align(d), ea = dtype_bytes(d->dtype);
-        if (misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
+        if (misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ea) ||
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(sinks, sizeof(float)))
             return NNOP_ERR_ALIGN;
     }
@@ -471,8 +474,8 @@ int nnop_fa_bwd_softcap(const nnop_fa_desc* d, const nnop_fa_opts* opts, const f
     if (workspace_bytes < bwd_workspace_bytes(*d)) return NNOP_ERR_WORKSPACE;
     {
         const size_t ta = tensor_align(d), ea = dtype_bytes(d->dtype);
-        if (misaligned(dq, ta) || misaligned(dk, ta) || misaligned(dv, ta) || misaligned(dpair, ta) || misaligned(d_o, ta) ||
-            misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ta) ||
+        if (misaligned(dq, ta) || misaligned(dk, ta) || misaligned(dv, ta) || misaligned(dpair, ea) || misaligned(d_o, ta) ||
+            misaligned(o, ta) || misaligned(q, ta) || misaligned(k, ta) || misaligned(v, ta) || misaligned(pair, ea) ||
             misaligned(ms, ea) || misaligned(ls, ea) || misaligned(workspace, 16) || misaligned(sinks, sizeof(float)) ||
             misaligned(dsinks, sizeof(float)))
             return NNOP_ERR_ALIGN;

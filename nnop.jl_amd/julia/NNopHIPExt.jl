@@ -67,7 +67,7 @@ function check(st::Cint, q, k, v)
     st == -3 && error("Only power-of-2 embedding dims are supported.")
     st == -4 && error("Number of query heads `$(size(q, 3))` must be divisible by number of KV heads `$(size(k, 3))`.")
     st == -7 && error("Failed to find groupsize for Flash Attention that satisfies Shared Memory constraint.")
-    st == -11 && error("libnnop_hip: a tensor base address is not 16-byte aligned (views with odd element offsets are not supported: copy them)")
+    st == -11 && error("libnnop_hip: a tensor base address is not 16-byte aligned (q, k, v, o, the gradients of q, k, v and the workspace; views of those with odd element offsets are not supported: copy them.  pair / dpair, ms, ls need their element size only)")
     msg = unsafe_string(ccall((:nnop_strerror, libnnop()), Cstring, (Cint,), st))
     error("libnnop_hip: $msg")
 end
@@ -439,7 +439,9 @@ function flash_attention_shard!(o, ms, ls, q::ROCArray{T,4}, k::ROCArray{T,4}, v
 end
 # (The indexing above copies the rectangle -- the simple, allocation-tolerant form.  The zero-copy form passes
 #  devptr(q) + s.q_off * sizeof(T), devptr(k) + s.kv_off * sizeof(T), ... with Ref(s.desc) straight to :nnop_fa_fwd / :nnop_fa_bwd,
-#  exactly as _flash_attention does with offset 0; the offsets are multiples of L * E elements, so 16-byte alignment is kept.)
+#  exactly as _flash_attention does with offset 0; the offsets are multiples of L * E elements, so 16-byte alignment is kept.
+#  A pair bias goes the same way, devptr(pair) + s.pair_off * sizeof(T): that offset is any multiple of the element size, which is
+#  all the library asks of pair / dpair.)
 
 # One process, all devices: qs[g], ks[g], vs[g] live on device g (replicas or batch slices of the global problem).
 function flash_attention_multi(qs::Vector, ks::Vector, vs::Vector; causal::Bool)

@@ -131,8 +131,8 @@ def test_debug_hook_is_locked_without_the_environment_switch():
 
 
 def test_misaligned_bases_are_refused_before_any_launch(pkg):
-    """NNOP_ERR_ALIGN: the MFMA kernels move q, k, v, o, the gradients, the bias and the workspace with 16-byte vector accesses and
-    LDS-DMA from the raw base.  Checked behind the descriptor and NULL checks, in front of the launch (so this runs without a GPU:
+    """NNOP_ERR_ALIGN: the MFMA kernels move q, k, v, o, the gradients and the workspace with 16-byte vector accesses and
+    LDS-DMA from the raw base (pair / dpair need the element size only: tests/test_zzzzzzzz_attn_arena_gpu.py).  Checked behind the descriptor and NULL checks, in front of the launch (so this runs without a GPU:
     the call returns before it touches the device)."""
     lib = pkg._lib.load()
     d = _desc(pkg)
