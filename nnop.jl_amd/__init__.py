@@ -8,8 +8,10 @@ Llama rotary embedding applied to q, k right before attention -- SURVEY.md secti
 mixture-of-experts gate and dispatch plan of the third library, ``include/nnop_hip_moe.h``, ``moe_data.py`` for the token
 permute and weighted combine of the fourth, ``include/nnop_hip_moe_data.h``, ``moe_gemm.py`` for the grouped expert GEMM of
 the fifth, ``include/nnop_hip_moe_gemm.h``, ``moe_linear.py`` for the expert linear layers (bias, [E, K, N] weights, accumulating
-gradients) of the sixth, ``include/nnop_hip_moe_linear.h``; ``_common.py`` for the call plumbing they all share and ``_lib.py``
-for the one loader of the six ctypes bindings), the
+gradients) of the sixth, ``include/nnop_hip_moe_linear.h``, ``moe_mx.py`` for the same layers on MXFP4 expert weights (packed blocks
+and scale bytes read where they lie, forward and the pullback to the rows) and the MXFP4 quantiser and dequantiser of the seventh,
+``include/nnop_hip_moe_mx.h``; ``_common.py`` for the call plumbing they all share and ``_lib.py``
+for the one loader of the seven ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -35,8 +37,10 @@ from .moe_gemm import (moe_grouped_gemm, _moe_grouped_gemm, grad_moe_grouped_gem
                        grad_moe_grouped_gemm_x_into, grad_moe_grouped_gemm_w_into)
 from .moe_linear import (moe_grouped_linear, _moe_grouped_linear, grad_moe_grouped_linear, moe_grouped_linear_into,
                          grad_moe_grouped_linear_x_into, grad_moe_grouped_linear_w_into, grad_moe_grouped_linear_b_into)
-from . import (_common, _lib, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, activations, losses, moe, moe_data,
-               moe_gemm, moe_linear, qknorm, shard, workmodel)
+from .moe_mx import (mxfp4_quantize, mxfp4_dequantize, moe_grouped_linear_mxfp4, _moe_grouped_linear_mxfp4,
+                     moe_grouped_linear_mxfp4_into, grad_moe_grouped_linear_mxfp4_x_into)
+from . import (_common, _lib, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, activations, losses, moe,
+               moe_data, moe_gemm, moe_linear, moe_mx, qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -54,5 +58,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "grad_moe_grouped_gemm_w_into", "moe_gemm",
            "moe_grouped_linear", "_moe_grouped_linear", "grad_moe_grouped_linear", "moe_grouped_linear_into",
            "grad_moe_grouped_linear_x_into", "grad_moe_grouped_linear_w_into", "grad_moe_grouped_linear_b_into", "moe_linear",
-           "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear"]
+           "mxfp4_quantize", "mxfp4_dequantize", "moe_grouped_linear_mxfp4", "_moe_grouped_linear_mxfp4",
+           "moe_grouped_linear_mxfp4_into", "grad_moe_grouped_linear_mxfp4_x_into", "moe_mx",
+           "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx"]
 __version__ = "0.1.0"

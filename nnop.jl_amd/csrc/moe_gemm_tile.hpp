@@ -1,7 +1,8 @@
-// moe_gemm_tile.hpp -- the one MFMA tile of the two grouped-GEMM libraries: libnnop_hip_moe_gemm.so (moe_gemm.hip) and
-// libnnop_hip_moe_linear.so (moe_linear.hip) instantiate it; nothing is linked between them.  gfx950 (MI355X) only.
+// moe_gemm_tile.hpp -- the one MFMA tile of the three grouped-GEMM libraries: libnnop_hip_moe_gemm.so (moe_gemm.hip),
+// libnnop_hip_moe_linear.so (moe_linear.hip) and libnnop_hip_moe_mx.so (moe_mx.hip) instantiate it; nothing is linked between them.
+// gfx950 (MI355X) only.
 //
-// moe_gemm_tile<T, PROD, ALIGNED, EPI, OutT> computes
+// moe_gemm_tile<T, PROD, ALIGNED, EPI, OutT, StageB> computes
 //     C[m][n] = epilogue( sum_r A(m, r) B(n, r) )
 // on a 128 x 128 output tile with 4 waves (2 x 2, 64 x 64 each, 4 x 4 MFMA tiles of 16 x 16) and fp32 accumulators.  The three products
 // differ in what m, n, r are and in how an operand lies in memory:
@@ -26,6 +27,11 @@
 //     EPI 2  + old           (PROD 2) the lane loads what C holds, masked like its store; the workgroups of an expert without rows
 //                            return before any load, so that expert's C keeps its bits
 // OutT is T, or float beside a 16-bit T (PROD 2: an fp32 weight gradient).
+//
+// StageB is how the B operand of PROD 0 / 1 gets from memory into the staging registers: by default Stage<T, TRB, ALIGNED>, which reads
+// elements of T.  Another policy (moe_mx.hip: packed MXFP4 weights) has the interface of Stage -- Src, Extra, origin(), advance(),
+// load(), write() -- and must hold in v[], when Stage's write() stores it, what the dense load of the expanded operand would have left;
+// the LDS image, the fragment reads, the MFMA order, the epilogue and the bounds are then those of the dense product.
 //
 // Nothing outside [0, S) x [0, ld) and the E weight matrices is touched whatever `offsets` holds: offsets are clamped into [0, S] where
 // they are read, and every loop bound is a descriptor field or such a clamped value.  Rows outside the tile's range (an expert's end,
@@ -114,7 +120,17 @@ template <typename T, bool TR, bool ALIGNED> struct Stage {
     static constexpr int XC = kTile / EPC;
     typedef T tvec __attribute__((ext_vector_type(EPC)));
     typedef T t4 __attribute__((ext_vector_type(4)));
+    typedef const T* Src;  // where an operand's step begins: (x = 0, r = 0)
+    struct Extra {};       // what a policy needs beyond GemmParams: nothing here
     tvec v[kPieces];
+
+    // the B operand of PROD 0 / 1: column tile n0 of expert e, and one reduction step further along r
+    static __device__ __forceinline__ Src origin(const GemmParams& p, const Extra&, long long e, int n0) {
+        return static_cast<const T*>(p.b) + (e * p.wstride + (TR ? (long long)n0 : n0 * p.ldb));
+    }
+    static __device__ __forceinline__ Src advance(Src b, const GemmParams& p, const Extra&) {
+        return b + (TR ? (kRowBytes / (int)sizeof(T)) * p.ldb : (long long)(kRowBytes / (int)sizeof(T)));
+    }
 
     __device__ __forceinline__ void load(const T* base, long long ld, int xleft, int rleft, int t) {
 #pragma unroll
@@ -161,8 +177,8 @@ template <typename T, bool TR, bool ALIGNED> struct Stage {
 static_assert(kPieces == 4, "the transposing write packs kPieces = 4 consecutive r");
 
 // The body of a workgroup, 64 KiB of LDS included.  tb is read for EPI 1 only.
-template <typename T, int PROD, bool ALIGNED, int EPI, typename OutT>
-__device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias tb) {
+template <typename T, int PROD, bool ALIGNED, int EPI, typename OutT, typename StageB = Stage<T, PROD != 0, ALIGNED>>
+__device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias tb, const typename StageB::Extra xb = {}) {
     static_assert(EPI == 0 || (EPI == 1 && PROD != 2) || (EPI == 2 && PROD == 2), "bias beside the row products, + old beside bwd_w");
     constexpr int EPC = 16 / (int)sizeof(T);
     constexpr int BK = kRowBytes / (int)sizeof(T);
@@ -180,11 +196,11 @@ __device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias
     const unsigned pos = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
 
     const T* a = static_cast<const T*>(p.a);
-    const T* b = static_cast<const T*>(p.b);
+    typename StageB::Src b;
     OutT* out = static_cast<OutT*>(p.out);
     const T* bias = nullptr;   // EPI 1: the bias of this tile's columns; stays null for a tile of +0
     int mleft, nleft, rtotal;  // rows and columns of the tile that exist (<= 128), length of the reduction
-    if (PROD != 2) {
+    if constexpr (PROD != 2) {
         const long long ti = pos % (unsigned)p.mt;
         const int ct = pos / (unsigned)p.mt;
         // wave 0 finds the (segment, tile) of row-tile slot ti: each lane sums the tiles of `per` consecutive segments, a scan over the
@@ -231,7 +247,7 @@ __device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias
         rtotal = expert ? p.R : 0;  // the rows in front of and behind the experts: a tile of +0
         const long long e = expert ? seg - 1 : 0;
         a += m0 * p.lda;
-        b += e * p.wstride + (PROD == 0 ? n0 * p.ldb : (long long)n0);
+        b = StageB::origin(p, xb, e, n0);
         out += m0 * p.ldc + n0;
         if (EPI == 1 && expert) bias = static_cast<const T*>(tb.bias) + e * tb.ld + n0;
     } else {
@@ -244,7 +260,7 @@ __device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias
         rtotal = hi > lo ? hi - lo : 0;
         if (EPI == 2 && rtotal == 0) return;  // nothing to add: what C holds stays, bit for bit
         a += lo * p.lda + m0;
-        b += lo * p.ldb + n0;
+        b = static_cast<const T*>(p.b) + (lo * p.ldb + n0);
         out += e * p.wstride + m0 * p.ldc + n0;
     }
 
@@ -256,10 +272,10 @@ __device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // one reduction step further along r: contiguous operands move BK columns, strided ones BK rows
-    const long long step_a = TRA ? BK * p.lda : (long long)BK, step_b = TRB ? BK * p.ldb : (long long)BK;
+    const long long step_a = TRA ? BK * p.lda : (long long)BK;
     const int steps = (int)(((long long)rtotal + BK - 1) / BK);
     Stage<T, TRA, ALIGNED> sa;
-    Stage<T, TRB, ALIGNED> sb;
+    StageB sb;
     if (steps > 0) {
         sa.load(a, p.lda, mleft, rtotal, t);
         sb.load(b, p.ldb, nleft, rtotal, t);
@@ -273,7 +289,7 @@ __device__ __forceinline__ void moe_gemm_tile(const GemmParams p, const TileBias
         const bool more = k + 1 < steps;
         if (more) {
             a += step_a;
-            b += step_b;
+            b = StageB::advance(b, p, xb);
             sa.load(a, p.lda, mleft, rtotal - (k + 1) * BK, t);
             sb.load(b, p.ldb, nleft, rtotal - (k + 1) * BK, t);
         }
