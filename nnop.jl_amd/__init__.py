@@ -11,8 +11,9 @@ the fifth, ``include/nnop_hip_moe_gemm.h``, ``moe_linear.py`` for the expert lin
 gradients) of the sixth, ``include/nnop_hip_moe_linear.h``, ``moe_mx.py`` for the same layers on MXFP4 expert weights (packed blocks
 and scale bytes read where they lie, forward and the pullback to the rows) and the MXFP4 quantiser and dequantiser of the seventh,
 ``include/nnop_hip_moe_mx.h``, ``moe_mx_decode.py`` for the weight-streaming forward of those layers at decode sizes (few rows per
-expert) of the eighth, ``include/nnop_hip_moe_mx_decode.h``; ``_common.py`` for the call plumbing they all share and ``_lib.py``
-for the one loader of the eight ctypes bindings), the
+expert) of the eighth, ``include/nnop_hip_moe_mx_decode.h``, ``moe_mx_decode_glu.py`` for that forward on a fused gate-up projection
+with the gated activation in its epilogue and the token gather in front of the ninth, ``include/nnop_hip_moe_mx_decode_glu.h``;
+``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the nine ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -41,8 +42,10 @@ from .moe_linear import (moe_grouped_linear, _moe_grouped_linear, grad_moe_group
 from .moe_mx import (mxfp4_quantize, mxfp4_dequantize, moe_grouped_linear_mxfp4, _moe_grouped_linear_mxfp4,
                      moe_grouped_linear_mxfp4_into, grad_moe_grouped_linear_mxfp4_x_into)
 from .moe_mx_decode import moe_decode_linear_mxfp4, _moe_decode_linear_mxfp4, moe_decode_linear_mxfp4_into
+from .moe_mx_decode_glu import moe_decode_glu_mxfp4, _moe_decode_glu_mxfp4, moe_decode_glu_mxfp4_into
 from . import (_common, _lib, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
-               activations, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, qknorm, shard, workmodel)
+               _lib_moe_mx_decode_glu, activations, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
+               qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -63,6 +66,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "mxfp4_quantize", "mxfp4_dequantize", "moe_grouped_linear_mxfp4", "_moe_grouped_linear_mxfp4",
            "moe_grouped_linear_mxfp4_into", "grad_moe_grouped_linear_mxfp4_x_into", "moe_mx",
            "moe_decode_linear_mxfp4", "_moe_decode_linear_mxfp4", "moe_decode_linear_mxfp4_into", "moe_mx_decode",
+           "moe_decode_glu_mxfp4", "_moe_decode_glu_mxfp4", "moe_decode_glu_mxfp4_into", "moe_mx_decode_glu",
            "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx",
-           "_lib_moe_mx_decode"]
+           "_lib_moe_mx_decode", "_lib_moe_mx_decode_glu"]
 __version__ = "0.1.0"

@@ -166,7 +166,7 @@ DEBUG_SYMBOLS = tuple(DEBUG_PROTOTYPES)
 
 
 def load_library(binding, label, version_name, version_symbol, optional=None):
-    """The load sequence of all seven bindings.  `binding` is the binding module: its LIB_PATH, EXPORTED_SYMBOLS, PROTOTYPES and version
+    """The load sequence of all nine bindings.  `binding` is the binding module: its LIB_PATH, EXPORTED_SYMBOLS, PROTOTYPES and version
     constant (`version_name`) are read now, not at import, and the library lands in its `_lib`.  dlopen, compare what `version_symbol`
     returns first -- a stale library may lack symbols the binding declares -- then require every exported symbol and declare the
     prototypes; those of `optional` only where the library has the symbol.  `label` names the version in the message."""

@@ -7,18 +7,11 @@
 //
 // Work: workgroup (e, c) is expert e and the output columns (weight rows) 256 c ... 256 c + 255, all of K; the grid is E ceil(N / 256),
 // fixed on the host.  offsets[e], offsets[e+1] are read here and clamped into [0, S].  Wave w owns kNT = 4 MFMA row tiles of 16 weight
-// rows, 64 in all.  A reduction step is 128 values of k = 4 blocks of 32: lane (r = lane % 16, q = lane / 16) loads, per row tile, the
-// 16 bytes of block 4 step + q of weight row r and that block's scale byte; mx_convert8 (moe_mx.hpp, the seventh library's conversion)
-// turns word i of the block into k = 32 q + 8 i ... 8 i + 7 of the step, which is the row operand of the i-th v_mfma_f32_16x16x32 of the
-// step as it stands.  The k order inside an MFMA is free where both operands agree, so the x operand of lane (m = lane % 16, q) is the
-// matching 64 contiguous bytes of row m: four 16-byte loads.  acc[tile][g] ends as 4 consecutive n (4 q ... 4 q + 3) of row m.
-//
-// The ring: kDepth steps of loads (kDepth kNT = 8 weight blocks of 16 bytes, their scale bytes, the x pieces) are in flight per wave; the
-// loop consumes slot d and refills it with step + kDepth.  Every load is unconditional, from an address clamped to a row and block that
-// exist (a slot m >= the pass's rows reads the pass's first row, which the lanes of slot 0 fetch anyway: no further traffic), and what
-// does not exist is replaced at the consumer: word 0 with scale byte 127 (+0) for a weight row >= N or a block >= K / 32, zeros for a row
-// slot beyond the expert or a block beyond K.  So the compiler sees straight-line loads consumed in issue order and waits with counted
-// vmcnt, and masking is by selection: no byte of another expert, of a row outside this expert or of padding enters a product.
+// rows, 64 in all.  The pass of a wave over K -- the ring of loads in flight, the clamped addresses, the selection at the consumer, the
+// MFMAs -- is decode_ring of moe_mx_decode_ring.hpp, which the ninth library (moe_mx_decode_glu.hip) instantiates too; this kernel gives
+// it the tiles n0 + 16 i, the x rows of the pass (a slot m >= the pass's rows reads the pass's first row, which the lanes of slot 0 fetch
+// anyway: no further traffic) and the store below.  acc[tile][g] ends as 4 consecutive n (4 q ... 4 q + 3) of row m.  Masking is by
+// selection: no byte of another expert, of a row outside this expert or of padding enters a product.
 //
 // Rows: an expert with up to 16 rows takes one accumulator group per tile in one pass over its weights, up to 32 two (the x pieces of the
 // second group ride in the same ring); more rows loop over passes of 32, which find the workgroup's 256 weight rows in L2.  The sum of
@@ -31,25 +24,14 @@
 // 0, those behind offsets[E] by the workgroups of expert E - 1, each in its own columns, before they look at their expert's rows; a
 // workgroup whose expert has no rows returns after that, before any weight load.
 #include "moe_mx_decode.hpp"
-#include "moe_mx.hpp"
-#include "moe_gemm_tile.hpp"
+#include "moe_mx_decode_ring.hpp"
 #include "host_common.hpp"
 #include <type_traits>
 
 namespace nnop {
 namespace {
 
-constexpr int kNT = 4;                       // MFMA row tiles (16 weight rows each) per wave
 constexpr int kWaveCols = 16 * kNT;
-constexpr int kStepBlocks = 4;               // a reduction step: 4 blocks of 32, one per k group of the MFMA
-// The ring depth in steps.  kDepth kNT = 8 weight loads of 16 bytes are in flight per lane, 8 KiB per wave; at the 2 waves per SIMD the
-// registers allow (profiles/r06/kernel_resources.txt) that is 64 KiB per CU, near the 72 KiB that hide most of an HBM miss (about 900
-// cycles) on this chip.  A third step costs about 54 VGPRs; it and a third wave per SIMD (96 KiB either way) were timed and changed
-// nothing: the depth is not what bounds this kernel.
-constexpr int kDepth = 2;
-// Accumulator groups (16 rows each) of one pass.  The count is chosen per expert on the device, inside one kernel, so the registers of
-// the largest count are every expert's: 4 groups would take the kernel to one wave per SIMD.
-constexpr int kMaxGroups = 2;
 static_assert(kWaveCols * (kThreads / 64) == kMoeMxDecodeCols, "four waves cover the workgroup's columns");
 
 struct DecodeParams {
@@ -84,25 +66,16 @@ template <typename T> __device__ __forceinline__ void zero_rows(const DecodePara
     }
 }
 
-// One pass of a wave: rows m0 ... m0 + rows - 1 (rows <= 16 G) of expert e against weight rows n0 ... n0 + 63, all of K.
+// One pass of a wave: rows m0 ... m0 + rows - 1 (rows <= 16 G) of expert e against weight rows n0 ... n0 + 63, all of K, on the ring of
+// moe_mx_decode_ring.hpp: tile i starts at weight row n0 + 16 i, a lane's x row of group g is row m0 + 16 g + lane % 16 (a slot beyond the
+// pass's rows reads the pass's first row, which the lanes of slot 0 fetch anyway: no further traffic), and the epilogue is the store below.
 template <typename T, bool XA, int G> __device__ __forceinline__ void decode_pass(const DecodeParams& p, int e, int n0, int m0, int rows, int lane) {
-    typedef T tvec __attribute__((ext_vector_type(8)));
     typedef T t4 __attribute__((ext_vector_type(4)));
     const int fr = lane & 15, fq = lane >> 4;
-    const int nb = p.K / kMxBlock;
-
-    // the lane's weight row of each tile and its x row of each group, clamped to ones that exist
-    const uint8_t* wq[kNT];
-    const uint8_t* ws[kNT];
-    bool wok[kNT];
+    const RingWeights w{p.blocks, p.scales, p.ld_q, p.ld_s, p.K, p.N};
+    int base[kNT], end[kNT];
 #pragma unroll
-    for (int i = 0; i < kNT; ++i) {
-        const int n = n0 + 16 * i + fr;
-        wok[i] = n < p.N;
-        const long long row = (long long)e * p.N + (wok[i] ? n : p.N - 1);
-        wq[i] = p.blocks + row * p.ld_q;
-        ws[i] = p.scales + row * p.ld_s;
-    }
+    for (int i = 0; i < kNT; ++i) base[i] = n0 + 16 * i, end[i] = p.N;
     const T* xr[G];
     bool xok[G];
 #pragma unroll
@@ -111,120 +84,42 @@ template <typename T, bool XA, int G> __device__ __forceinline__ void decode_pas
         xok[g] = m < rows;
         xr[g] = static_cast<const T*>(p.xs) + (long long)(m0 + (xok[g] ? m : 0)) * p.ld_x;
     }
-
-    struct Slot {
-        uint4 w[kNT];
-        uint32_t e[kNT];
-        tvec x[G][4];
-    };
-    Slot ring[kDepth];
-    f32x4 acc[kNT][G];
-#pragma unroll
-    for (int i = 0; i < kNT; ++i)
-#pragma unroll
-        for (int g = 0; g < G; ++g) acc[i][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // loads only: nothing here waits for what it fetched
-    auto load = [&](Slot& s, int step) {
-        const int b = min(kStepBlocks * step + fq, nb - 1);
+    decode_ring<T, XA, G>(w, e, base, end, xr, xok, lane, [&](const f32x4 (&acc)[kNT][G]) {
+        // acc[i][g][j] is ys[m0 + 16 g + fr][n0 + 16 i + 4 fq + j]
+        const T* bias = p.bias ? static_cast<const T*>(p.bias) + e * p.ld_b : nullptr;
 #pragma unroll
         for (int i = 0; i < kNT; ++i) {
-            s.w[i] = *reinterpret_cast<const uint4*>(wq[i] + 16 * b);
-            s.e[i] = ws[i][b];
-        }
+            const int n = n0 + 16 * i + 4 * fq;
+            if (n >= p.N) continue;
+            const bool whole = p.vec && n + 3 < p.N;
+            f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (bias != nullptr) {
+                if (whole) {
+                    const t4 v = *reinterpret_cast<const t4*>(bias + n);
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const T* src = xr[g] + kMxBlock * b;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (XA) {
-                    s.x[g][i] = *reinterpret_cast<const tvec*>(src + 8 * i);
+                    for (int j = 0; j < 4; ++j) bv[j] = (float)v[j];
                 } else {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) s.x[g][i][j] = src[8 * i + j];
+                    for (int j = 0; j < 4; ++j)
+                        if (n + j < p.N) bv[j] = (float)bias[n + j];
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int m = 16 * g + fr;
+                if (m >= rows) continue;
+                const f32x4 v = acc[i][g] + bv;
+                T* dst = static_cast<T*>(p.ys) + (long long)(m0 + m) * p.ld_y + n;
+                if (whole) {
+                    *reinterpret_cast<t4*>(dst) = t4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (n + j < p.N) dst[j] = (T)v[j];
                 }
             }
         }
-    };
-    // selection, conversion, MFMAs: word i of a block beside piece i of the x rows
-    auto consume = [&](const Slot& s, int step) {
-        const bool bok = kStepBlocks * step + fq < nb;
-        tvec zero;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) zero[j] = (T)0.f;
-        tvec xv[G][4];
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xv[g][i] = xok[g] && bok ? s.x[g][i] : zero;
-#pragma unroll
-        for (int i = 0; i < kNT; ++i) {
-            const bool ok = wok[i] && bok;
-            const uint32_t sc = ok ? s.e[i] : 127u;
-            const uint32_t words[4] = {ok ? s.w[i].x : 0u, ok ? s.w[i].y : 0u, ok ? s.w[i].z : 0u, ok ? s.w[i].w : 0u};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const tvec a = mx_convert8<T>(words[j], sc);
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[i][g] = Mma<T>::run(a, xv[g][j], acc[i][g]);  // rows of the result: n, columns: m
-            }
-        }
-    };
-
-    const int steps = (nb + kStepBlocks - 1) / kStepBlocks;
-#pragma unroll
-    for (int d = 0; d < kDepth; ++d) load(ring[d], d);
-    // A step beyond the last one adds +0 to every accumulator; how many there are depends on K alone.  pin() keeps the loads of a slot
-    // between the work on two slots (the empty statement for the optimiser, the scheduling barrier for the instruction scheduler): left
-    // alone, the compiler gathers the loads of an iteration, waits for all of them and computes, and the ring is gone.
-    auto pin = [] {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    for (int s0 = 0; s0 < steps; s0 += kDepth) {
-#pragma unroll
-        for (int d = 0; d < kDepth; ++d) {
-            pin();
-            consume(ring[d], s0 + d);
-            pin();
-            load(ring[d], s0 + d + kDepth);
-        }
-    }
-
-    // acc[i][g][j] is ys[m0 + 16 g + fr][n0 + 16 i + 4 fq + j]
-    const T* bias = p.bias ? static_cast<const T*>(p.bias) + e * p.ld_b : nullptr;
-#pragma unroll
-    for (int i = 0; i < kNT; ++i) {
-        const int n = n0 + 16 * i + 4 * fq;
-        if (n >= p.N) continue;
-        const bool whole = p.vec && n + 3 < p.N;
-        f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (bias != nullptr) {
-            if (whole) {
-                const t4 v = *reinterpret_cast<const t4*>(bias + n);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bv[j] = (float)v[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (n + j < p.N) bv[j] = (float)bias[n + j];
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int m = 16 * g + fr;
-            if (m >= rows) continue;
-            const f32x4 v = acc[i][g] + bv;
-            T* dst = static_cast<T*>(p.ys) + (long long)(m0 + m) * p.ld_y + n;
-            if (whole) {
-                *reinterpret_cast<t4*>(dst) = t4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (n + j < p.N) dst[j] = (T)v[j];
-            }
-        }
-    }
+    });
 }
 
 template <typename T, bool XA> __global__ __launch_bounds__(kThreads) void moe_mx_decode_kernel(const DecodeParams p) {
