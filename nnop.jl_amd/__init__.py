@@ -14,8 +14,9 @@ and scale bytes read where they lie, forward and the pullback to the rows) and t
 expert) of the eighth, ``include/nnop_hip_moe_mx_decode.h``, ``moe_mx_decode_glu.py`` for that forward on a fused gate-up projection
 with the gated activation in its epilogue and the token gather in front of the ninth, ``include/nnop_hip_moe_mx_decode_glu.h``,
 ``decode_attn.py`` for the attention of a decode step over a KV cache (split-KV, packed GQA, sinks, lengths on the device) of the
-tenth, ``include/nnop_hip_decode_attn.h``;
-``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the ten ctypes bindings), the
+tenth, ``include/nnop_hip_decode_attn.h``, ``decode_attn_fp8.py`` for that attention over a cache of one-byte E4M3 codes with a scale
+per KV head, expanded in registers, of the eleventh, ``include/nnop_hip_decode_attn_fp8.h``;
+``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the eleven ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -46,8 +47,9 @@ from .moe_mx import (mxfp4_quantize, mxfp4_dequantize, moe_grouped_linear_mxfp4,
 from .moe_mx_decode import moe_decode_linear_mxfp4, _moe_decode_linear_mxfp4, moe_decode_linear_mxfp4_into
 from .moe_mx_decode_glu import moe_decode_glu_mxfp4, _moe_decode_glu_mxfp4, moe_decode_glu_mxfp4_into
 from .decode_attn import decode_attention, decode_attention_into, decode_attention_plan
-from . import (_common, _lib, _lib_decode_attn, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
-               _lib_moe_mx_decode_glu, activations, decode_attn, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
+from .decode_attn_fp8 import decode_attention_fp8, decode_attention_fp8_into, decode_attention_fp8_plan
+from . import (_common, _lib, _lib_decode_attn, _lib_decode_attn_fp8, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
+               _lib_moe_mx_decode_glu, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
                qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
@@ -71,6 +73,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "moe_decode_linear_mxfp4", "_moe_decode_linear_mxfp4", "moe_decode_linear_mxfp4_into", "moe_mx_decode",
            "moe_decode_glu_mxfp4", "_moe_decode_glu_mxfp4", "moe_decode_glu_mxfp4_into", "moe_mx_decode_glu",
            "decode_attention", "decode_attention_into", "decode_attention_plan", "decode_attn", "_lib_decode_attn",
+           "decode_attention_fp8", "decode_attention_fp8_into", "decode_attention_fp8_plan", "decode_attn_fp8", "_lib_decode_attn_fp8",
            "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx",
            "_lib_moe_mx_decode", "_lib_moe_mx_decode_glu"]
 __version__ = "0.1.0"
