@@ -20,11 +20,13 @@ a paged cache (a pool of pages and a block table per sequence, read where they l
 ``paged_prefill.py`` for the prefill step over that cache -- a variable number of new tokens per sequence, packed token-major, behind a
 cached prefix (a prompt, a chunk of a chunked prefill, speculative verification of more than 16 rows); row blocks of 128 / G tokens
 times the G heads of a KV head, 32-key tiles shared through two LDS images, scores transposed on the 32x32x16 MFMA, table entries
-fetched a tile ahead, each workgroup finding its block by a search over cu_seqlens_q (no workspace); forward only, no FP8 pages, no
+fetched a tile ahead, each workgroup finding its block by a search over cu_seqlens_q (no workspace); forward only, no
 split-KV -- of the thirteenth, ``include/nnop_hip_paged_prefill.h``, ``paged_attn_fp8.py`` for the decode step over pages of one-byte
 E4M3 codes -- the eleventh library's data path behind the twelfth's block table, the table entries of each of the four ring slots
-fetched a refill ahead -- of the fourteenth, ``include/nnop_hip_paged_attn_fp8.h``;
-``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the fourteen ctypes bindings), the
+fetched a refill ahead -- of the fourteenth, ``include/nnop_hip_paged_attn_fp8.h``, ``paged_prefill_fp8.py`` for the prefill step over
+those pages of codes -- the thirteenth library's kernel with the codes expanded to q's type in the registers that stage a tile for LDS,
+once per tile and off the loop's critical path -- of the fifteenth, ``include/nnop_hip_paged_prefill_fp8.h``;
+``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the fifteen ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -59,9 +61,10 @@ from .decode_attn_fp8 import decode_attention_fp8, decode_attention_fp8_into, de
 from .paged_attn import paged_decode_attention, paged_decode_attention_into, paged_decode_attention_plan
 from .paged_prefill import paged_prefill_attention, paged_prefill_attention_into, paged_prefill_attention_plan
 from .paged_attn_fp8 import paged_decode_attention_fp8, paged_decode_attention_fp8_into, paged_decode_attention_fp8_plan
+from .paged_prefill_fp8 import paged_prefill_attention_fp8, paged_prefill_attention_fp8_into, paged_prefill_attention_fp8_plan
 from . import (_common, _lib, _lib_decode_attn, _lib_decode_attn_fp8, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
-               _lib_moe_mx_decode_glu, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_prefill, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
-               paged_attn, paged_attn_fp8, paged_prefill, qknorm, shard, workmodel)
+               _lib_moe_mx_decode_glu, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_prefill, _lib_paged_prefill_fp8, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
+               paged_attn, paged_attn_fp8, paged_prefill, paged_prefill_fp8, qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -89,6 +92,8 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "paged_prefill_attention", "paged_prefill_attention_into", "paged_prefill_attention_plan", "paged_prefill", "_lib_paged_prefill",
            "paged_decode_attention_fp8", "paged_decode_attention_fp8_into", "paged_decode_attention_fp8_plan", "paged_attn_fp8",
            "_lib_paged_attn_fp8",
+           "paged_prefill_attention_fp8", "paged_prefill_attention_fp8_into", "paged_prefill_attention_fp8_plan", "paged_prefill_fp8",
+           "_lib_paged_prefill_fp8",
            "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx",
            "_lib_moe_mx_decode", "_lib_moe_mx_decode_glu"]
 __version__ = "0.1.0"

@@ -1,5 +1,6 @@
 // paged_prefill.hpp -- what the C boundary (nnop_paged_prefill_capi.cpp) and the kernels (paged_prefill.hip) of
-// libnnop_hip_paged_prefill.so share: the row block, the key tile and the two figures the host derives from them.
+// libnnop_hip_paged_prefill.so share: the row block, the key tile and the two figures the host derives from them.  The fifteenth library
+// (paged_prefill_fp8.hpp) reads the constants and the two figures too, on its own descriptor D: header-only, nothing is linked.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/nnop_hip_paged_prefill.h"
@@ -13,9 +14,9 @@ static_assert(kPpRows == 32 * kPpWaves, "a wave owns 32 rows");
 static_assert(sizeof(nnop_paged_prefill_desc) == 136, "the twelfth library's 104 bytes and the strides of q and o");
 
 // tokens of a row block: its rows are these tokens times the G query heads of a KV head; 128 - TB G < G rows are dead
-static inline int paged_prefill_block_tokens(const nnop_paged_prefill_desc& d) { return kPpRows / (d.qh / d.kh); }
+template <typename D> static inline int paged_prefill_block_tokens(const D& d) { return kPpRows / (d.qh / d.kh); }
 // the bound of sum_b ceil(n_b / TB) that the grid is sized by: host values alone
-static inline long long paged_prefill_max_blocks(const nnop_paged_prefill_desc& d) {
+template <typename D> static inline long long paged_prefill_max_blocks(const D& d) {
     return (long long)d.tokens / paged_prefill_block_tokens(d) + d.batch;
 }
 
