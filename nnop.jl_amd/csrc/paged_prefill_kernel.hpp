@@ -40,6 +40,13 @@
 // (thread tid holds piece tid % RC of row tid / RC, and of the rows kThreads / RC further); CH, the pieces of K, and of V, a thread
 // moves per tile; COLS, the elements of a piece; reg, the registers that hold one from its load to its store; load(); store(), which
 // writes the piece's 2 COLS bytes of the image; scale2(), the factor of the scores; out_factor(), the factor of the epilogue.
+//
+// A Part names which of a block's key tiles a workgroup walks and what it leaves behind.  PpWhole, the default: all of them, and the
+// finished rows (sink, division, one rounding) in o and lse.  PpChunk (libnnop_hip_paged_prefill_split.so, paged_prefill_split.hip):
+// the workgroups of a block are `splits` in number, chunk c = blockIdx.x % splits walks tiles t_lo + c per ... of the block's
+// t_lo ... t_hi, per = ceil(n / splits), and every live row leaves its fp32 un-normalised O and its (m, l) of the base-2 domain in a
+// workspace for a merge kernel.  A Part has: kPartial; group(), the (slot, KV head) index of the workgroup; first() and last(), the
+// tile range; finish(), the partial epilogue (never called when kPartial is false).
 #pragma once
 #include <type_traits>
 #include "paged_prefill.hpp"
@@ -97,7 +104,49 @@ template <typename T, int E> struct PpStage16 {
     static __device__ __forceinline__ float out_factor(float inv, const Params&, int) { return inv; }
 };
 
-template <typename T, int E, typename Stage> __device__ __forceinline__ void paged_prefill_body(const typename Stage::Params& p) {
+// every tile of the block; the epilogue below finishes the rows
+struct PpWhole {
+    static constexpr bool kPartial = false;
+    __device__ __forceinline__ unsigned group(unsigned block) const { return block; }
+    __device__ __forceinline__ int first(int t_lo, int) const { return t_lo; }
+    __device__ __forceinline__ int last(int, int t_hi) const { return t_hi; }
+    template <int E, typename Acc>
+    __device__ __forceinline__ void finish(const Acc*, float, float, long long, int, int, int) const {}
+};
+
+// chunk blockIdx.x % splits of the block's tiles; o_part [splits][T][QH][E] and ml_part [splits][T][QH][2] fp32 behind it, so that the
+// 16-byte stores of a lane's four consecutive columns stay aligned
+struct PpChunk {
+    static constexpr bool kPartial = true;
+    float* o_part;
+    float* ml_part;
+    int splits;
+    __device__ __forceinline__ int chunk() const { return blockIdx.x % splits; }
+    __device__ __forceinline__ unsigned group(unsigned block) const { return block / splits; }
+    __device__ __forceinline__ int per(int t_lo, int t_hi) const { return (max(t_hi - t_lo + 1, 0) + splits - 1) / splits; }
+    __device__ __forceinline__ int first(int t_lo, int t_hi) const { return t_lo + chunk() * per(t_lo, t_hi); }
+    // behind the block's last tile, or with per = 0, the chunk has no tile: last() < first()
+    __device__ __forceinline__ int last(int t_lo, int t_hi) const { return min(first(t_lo, t_hi) + per(t_lo, t_hi) - 1, t_hi); }
+    // A live row's (m, l), and its O unless it saw no key in the chunk (m = -inf, l = 0): the merge selects such a chunk out by its l
+    // and never reads that O.  Accumulator element 4 j + c of block et is column 32 et + 8 j + 4 fh + c, as in the epilogue below.
+    template <int E, typename Acc>
+    __device__ __forceinline__ void finish(const Acc* oacc, float m_run, float l_run, long long tok, int T, int QH, int head) const {
+        const int fh = (threadIdx.x & 63) >> 5;
+        const long long row = ((long long)chunk() * T + tok) * QH + head;
+        if (fh == 0) *reinterpret_cast<float2*>(ml_part + 2 * row) = float2{m_run, l_run};
+        if (!(l_run > 0.f)) return;
+        float* orow = o_part + row * E + 4 * fh;
+#pragma unroll
+        for (int et = 0; et < E / 32; ++et)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                *reinterpret_cast<float4*>(orow + 32 * et + 8 * j) =
+                    float4{oacc[et][4 * j], oacc[et][4 * j + 1], oacc[et][4 * j + 2], oacc[et][4 * j + 3]};
+    }
+};
+
+template <typename T, int E, typename Stage, typename Part = PpWhole>
+__device__ __forceinline__ void paged_prefill_body(const typename Stage::Params& p, const Part part = Part{}) {
     typedef typename Pp<T>::frag frag;
     typedef typename Stage::elem elem;
     constexpr float kNegInf = kPpNegInf, kLog2e = kPpLog2e, kLn2 = kPpLn2;
@@ -116,7 +165,8 @@ template <typename T, int E, typename Stage> __device__ __forceinline__ void pag
 
     const int tid = threadIdx.x, lane = tid & 63, fn = lane & 31, fh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform to the compiler: the table address follows
-    const int kvh = blockIdx.x % p.KH, slot = blockIdx.x / p.KH;
+    const unsigned group = part.group(blockIdx.x);
+    const int kvh = group % p.KH, slot = group / p.KH;
     auto cu_at = [&](int i) { return min(max(p.cu[i], 0), p.T); };
 
     // ---- which block: the first sequence whose inclusive count of blocks exceeds the slot ----
@@ -149,7 +199,8 @@ template <typename T, int E, typename Stage> __device__ __forceinline__ void pag
     const int p_last = pos0 + ntok - 1;
     const int seq_lo = p.window < 0 ? 0 : max(0, max(hi - nb, 0) - p.window);  // the first key any query of the sequence sees
     const int lo = p.window < 0 ? 0 : max(0, max(pos0, 0) - p.window);
-    const int t_lo = lo / kPpTile, t_hi = p_last >= 0 ? p_last / kPpTile : -1;  // inclusive; none if every row stands below 0
+    const int blk_t_lo = lo / kPpTile, blk_t_hi = p_last >= 0 ? p_last / kPpTile : -1;  // inclusive; none if every row stands below 0
+    const int t_lo = part.first(blk_t_lo, blk_t_hi), t_hi = part.last(blk_t_lo, blk_t_hi);  // what this workgroup walks of them
 
     // the query row of this lane, and what the wave's rows see between them
     const int r = 32 * wave + fn, rtok = r / p.G, rg = r - rtok * p.G;
@@ -303,6 +354,10 @@ template <typename T, int E, typename Stage> __device__ __forceinline__ void pag
         __syncthreads();  // the other image is whole, and this one has been read by every wave
     }
     if (!row_ok) return;
+    if constexpr (Part::kPartial) {
+        part.template finish<E>(oacc, m_run, l_run, tok, p.T, p.QH, head);
+        return;
+    }
 
     // the sink joins as one more column, then divide, round once, store
     const float sink_e = p.sinks ? p.sinks[head] : kNegInf, sink = sink_e * kLog2e;
