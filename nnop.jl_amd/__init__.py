@@ -28,8 +28,11 @@ those pages of codes -- the thirteenth library's kernel with the codes expanded 
 once per tile and off the loop's critical path -- of the fifteenth, ``include/nnop_hip_paged_prefill_fp8.h``,
 ``paged_prefill_split.py`` for the thirteenth library's prefill step with split-KV -- few new tokens behind a long context: every row
 block's key tiles cut into chunks, a workgroup each running the same kernel text over its chunk, fp32 partial results in a workspace and
-a merge kernel of one wave per (token, head) row -- of the sixteenth, ``include/nnop_hip_paged_prefill_split.h``;
-``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the sixteen ctypes bindings), the
+a merge kernel of one wave per (token, head) row -- of the sixteenth, ``include/nnop_hip_paged_prefill_split.h``,
+``paged_kv_write.py`` for the write side of that cache -- the new tokens' K and V rows into their pages in one launch, bit for bit into a
+16-bit pool or as E4M3 codes by the project's one quantisation rule, a wave per token with its sequence, position and table entry in
+scalar registers and its lanes moving 16-byte pieces -- of the seventeenth, ``include/nnop_hip_paged_kv_write.h``;
+``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the seventeen ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -66,9 +69,10 @@ from .paged_prefill import paged_prefill_attention, paged_prefill_attention_into
 from .paged_attn_fp8 import paged_decode_attention_fp8, paged_decode_attention_fp8_into, paged_decode_attention_fp8_plan
 from .paged_prefill_fp8 import paged_prefill_attention_fp8, paged_prefill_attention_fp8_into, paged_prefill_attention_fp8_plan
 from .paged_prefill_split import paged_prefill_attention_split, paged_prefill_attention_split_into, paged_prefill_attention_split_plan
+from .paged_kv_write import paged_kv_cache_write
 from . import (_common, _lib, _lib_decode_attn, _lib_decode_attn_fp8, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
-               _lib_moe_mx_decode_glu, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_prefill, _lib_paged_prefill_fp8, _lib_paged_prefill_split, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
-               paged_attn, paged_attn_fp8, paged_prefill, paged_prefill_fp8, paged_prefill_split, qknorm, shard, workmodel)
+               _lib_moe_mx_decode_glu, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_kv_write, _lib_paged_prefill, _lib_paged_prefill_fp8, _lib_paged_prefill_split, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
+               paged_attn, paged_attn_fp8, paged_kv_write, paged_prefill, paged_prefill_fp8, paged_prefill_split, qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -100,6 +104,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "_lib_paged_prefill_fp8",
            "paged_prefill_attention_split", "paged_prefill_attention_split_into", "paged_prefill_attention_split_plan", "paged_prefill_split",
            "_lib_paged_prefill_split",
+           "paged_kv_cache_write", "paged_kv_write", "_lib_paged_kv_write",
            "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx",
            "_lib_moe_mx_decode", "_lib_moe_mx_decode_glu"]
 __version__ = "0.1.0"
