@@ -31,8 +31,12 @@ block's key tiles cut into chunks, a workgroup each running the same kernel text
 a merge kernel of one wave per (token, head) row -- of the sixteenth, ``include/nnop_hip_paged_prefill_split.h``,
 ``paged_kv_write.py`` for the write side of that cache -- the new tokens' K and V rows into their pages in one launch, bit for bit into a
 16-bit pool or as E4M3 codes by the project's one quantisation rule, a wave per token with its sequence, position and table entry in
-scalar registers and its lanes moving 16-byte pieces -- of the seventeenth, ``include/nnop_hip_paged_kv_write.h``;
-``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the seventeen ctypes bindings), the
+scalar registers and its lanes moving 16-byte pieces -- of the seventeenth, ``include/nnop_hip_paged_kv_write.h``,
+``mla_decode.py`` for the decode step of multi-head latent attention (DeepSeek's MLA, weight-absorbed) over a paged latent cache -- one
+576-wide row per key that is the key and the value of up to 128 heads, a 32-key tile fetched once per workgroup into one of two LDS
+images and read two ways, row-wise for the scores and through the transposing LDS read for the values, 16 heads per wave -- of the
+eighteenth, ``include/nnop_hip_mla_decode.h``;
+``_common.py`` for the call plumbing they all share and ``_lib.py`` for the one loader of the eighteen ctypes bindings), the
 (batch, kv-head) sharding used for multi-GPU runs (``shard.py``) and the Julia package-extension
 shim (``julia/``, source only: no Julia in this image).
 
@@ -70,9 +74,10 @@ from .paged_attn_fp8 import paged_decode_attention_fp8, paged_decode_attention_f
 from .paged_prefill_fp8 import paged_prefill_attention_fp8, paged_prefill_attention_fp8_into, paged_prefill_attention_fp8_plan
 from .paged_prefill_split import paged_prefill_attention_split, paged_prefill_attention_split_into, paged_prefill_attention_split_plan
 from .paged_kv_write import paged_kv_cache_write
+from .mla_decode import mla_decode_attention, mla_decode_attention_into, mla_decode_attention_plan
 from . import (_common, _lib, _lib_decode_attn, _lib_decode_attn_fp8, _lib_ext, _lib_moe, _lib_moe_data, _lib_moe_gemm, _lib_moe_linear, _lib_moe_mx, _lib_moe_mx_decode,
-               _lib_moe_mx_decode_glu, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_kv_write, _lib_paged_prefill, _lib_paged_prefill_fp8, _lib_paged_prefill_split, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
-               paged_attn, paged_attn_fp8, paged_kv_write, paged_prefill, paged_prefill_fp8, paged_prefill_split, qknorm, shard, workmodel)
+               _lib_moe_mx_decode_glu, _lib_mla_decode, _lib_paged_attn, _lib_paged_attn_fp8, _lib_paged_kv_write, _lib_paged_prefill, _lib_paged_prefill_fp8, _lib_paged_prefill_split, activations, decode_attn, decode_attn_fp8, losses, moe, moe_data, moe_gemm, moe_linear, moe_mx, moe_mx_decode, moe_mx_decode_glu,
+               mla_decode, paged_attn, paged_attn_fp8, paged_kv_write, paged_prefill, paged_prefill_fp8, paged_prefill_split, qknorm, shard, workmodel)
 
 __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_attention",
            "shared_memory", "bwd_workspace_bytes", "fa_fwd_into", "fa_bwd_into", "LlamaRotaryEmbedding", "llama_rope", "_llama_rope", "grad_llama_rope", "llama_rope_into",
@@ -105,6 +110,7 @@ __all__ = ["NNopError", "flash_attention", "_flash_attention", "grad_flash_atten
            "paged_prefill_attention_split", "paged_prefill_attention_split_into", "paged_prefill_attention_split_plan", "paged_prefill_split",
            "_lib_paged_prefill_split",
            "paged_kv_cache_write", "paged_kv_write", "_lib_paged_kv_write",
+           "mla_decode_attention", "mla_decode_attention_into", "mla_decode_attention_plan", "mla_decode", "_lib_mla_decode",
            "shard", "workmodel", "_common", "_lib", "_lib_ext", "_lib_moe", "_lib_moe_data", "_lib_moe_gemm", "_lib_moe_linear", "_lib_moe_mx",
            "_lib_moe_mx_decode", "_lib_moe_mx_decode_glu"]
 __version__ = "0.1.0"

@@ -2,7 +2,7 @@
 
 This is the same binding, call for call, that the Julia extension in ``julia/NNopHIPExt.jl``
 makes with ``ccall``.  There is NO fallback: if the shared library is missing or a symbol is
-absent the import of the product path raises.  ``load_library`` is the load sequence of this binding and of the sixteen
+absent the import of the product path raises.  ``load_library`` is the load sequence of this binding and of the seventeen
 side bindings (``_lib_ext``, ``_lib_moe`` ... ``_lib_paged_prefill_split``, ``_lib_paged_kv_write``).
 """
 from __future__ import annotations
@@ -166,7 +166,7 @@ DEBUG_SYMBOLS = tuple(DEBUG_PROTOTYPES)
 
 
 def load_library(binding, label, version_name, version_symbol, optional=None):
-    """The load sequence of all seventeen bindings.  `binding` is the binding module: its LIB_PATH, EXPORTED_SYMBOLS, PROTOTYPES and version
+    """The load sequence of all eighteen bindings.  `binding` is the binding module: its LIB_PATH, EXPORTED_SYMBOLS, PROTOTYPES and version
     constant (`version_name`) are read now, not at import, and the library lands in its `_lib`.  dlopen, compare what `version_symbol`
     returns first -- a stale library may lack symbols the binding declares -- then require every exported symbol and declare the
     prototypes; those of `optional` only where the library has the symbol.  `label` names the version in the message."""
